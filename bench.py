@@ -6,9 +6,11 @@ One "step" = one pass of the hot path over one batch of synthetic tiles per GPU 
   -> greedy decode of exactly 128 tokens (EOS ignored) -> raster tail (union of 4 756^2 masks -> nearest 768^2 -> IoU).
 
 Default workload (the headline `value`) = BASELINE.json configs[2]: SocioReasoner-3B bf16, one MI355X, 32 rows in flight, CONTINUOUS BATCHING
-(overlapped admission): every step serves 4 x 32 tile requests through 32 batch rows.  The same command also times configs[1] (batch 1) and
-reports it under `latency_b1` of the same JSON line.  `--batch 1` makes configs[1] the headline; `--static` replaces the scheduler by one
-static batch per step.  Inputs (tiles, masks, weights) are resident in HBM before timing.
+(overlapped admission): every step serves 4 x 32 tile requests through 32 batch rows.  A plain run sets up, warms up, times --steps steps and
+prints the line; `--full` also times configs[1] (batch 1) under `latency_b1`, the other side measurements, the roofline object and the CPU
+baselines, all outside the timed region.  `--dump-outputs DIR` writes the last timed step's results as .npy files.  `--batch 1` makes
+configs[1] the headline; `--static` replaces the scheduler by one static batch per step.  Inputs (tiles, masks, weights) are resident in HBM
+before timing.
 Multi-GPU: one process per GPU (torchrun or `--gpus N` self-launch), tiles sharded data-parallel, no data-path collective while generating, one
 RCCL all-gather of the per-tile results (tokens + IoU counts) per step -> weak scaling.  The parts live in bench/ (see bench/__init__.py).
 """
@@ -27,7 +29,7 @@ sys.path.insert(0, ROOT)
 from bench import baselines, line, roofline, side  # noqa: E402
 from bench.common import clean, parse_args  # noqa: E402
 from bench.launch import self_launch  # noqa: E402
-from bench.workload import Workload  # noqa: E402
+from bench.workload import Workload, dump_outputs  # noqa: E402
 
 
 def main():
@@ -63,8 +65,13 @@ def main():
     dp.barrier()
     dt = dp.all_reduce_max(time.perf_counter() - t0, dev)
 
-    # ---- side measurements (rank 0 of an N = 1 run; none of them inside the timed region) and the line
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(res, args.dump_outputs)
+
+    # ---- --full: side measurements (rank 0 of an N = 1 run; none of them inside the timed region), roofline, CPU baselines; then the line
+    if rank == 0 and not args.full:
+        print(json.dumps(clean(line.assemble(wl, dt, res))), flush=True)
+    elif rank == 0:
         extras = world == 1 and not args.no_latency
         plain = B == 32 and args.tile == 448 and not args.pair and not args.fp8          # the headline configuration itself
         sd = {"static_batch": side.static_batch(wl) if wl.continuous and not args.no_latency else None,

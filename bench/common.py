@@ -48,7 +48,7 @@ def parse_args(argv=None):
     ap.add_argument("--poll-ragged", type=int, default=4, help="the same for the ragged phase (0 = --poll): rows that end on different steps are refilled "
                     "sooner "
                     "with short rounds -- measured 59.8 / 60.8 / 62.1 tiles/s at 16 / 8 / 4")
-    ap.add_argument("--no-latency", action="store_true", help="skip the side measurements (static batch, drained step, ragged, batch 1, ...)")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the side measurements (static batch, drained step, ragged, batch 1, ...)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sam", action="store_true", help="skip the SAM2 (seg_infer) timing")
     ap.add_argument("--no-more-rows", action="store_true", help="skip the 64- and 128-row points (child processes)")
@@ -64,6 +64,11 @@ def parse_args(argv=None):
     ap.add_argument("--gather-logits", action="store_true",
                     help="verification mode (static batch): all-gather the float32 logits of every decode step (north_star's literal exchange)")
     ap.add_argument("--pipeline-samples", type=int, default=250, help="samples of the two-stage pipeline leg (the reference's rollout_batch_size is 250)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline (off by default): the side measurements (static batch, "
+                    "drained step, 64 / 128 rows, ragged, SAM2, pipeline, batch 1), the roofline object (launch replay, rocprofv3 child passes) and the "
+                    "CPU baselines; the --no-* options above trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (per-tile "
+                    "greedy tokens and IoU counts, all tiles of all ranks in tile order) as DIR/<name>.npy in float64")
     args = ap.parse_args(argv)
     if args.fp8_mx:
         args.fp8 = True

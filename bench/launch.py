@@ -29,6 +29,9 @@ def self_launch(args, script):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     # N schedulers + N poll loops share this host: give every rank its share of the cores for its intra-op pool (torch.distributed.run would
-    # set OMP_NUM_THREADS=1; the collator and the PNG writers of the pipeline use a few threads), never more than 8
-    env.setdefault("OMP_NUM_THREADS", str(max(1, min(8, (os.cpu_count() or args.gpus) // args.gpus))))
+    # set OMP_NUM_THREADS=1; the collator and the PNG writers of the pipeline use a few threads), never more than 8.  The cores are this
+    # process's OMP_NUM_THREADS when it has one (the whole job's budget, split over the ranks), else the cores it may run on
+    budget = env.get("OMP_NUM_THREADS", "")
+    budget = int(budget) if budget.isdigit() and int(budget) > 0 else len(os.sched_getaffinity(0))
+    env["OMP_NUM_THREADS"] = str(max(1, min(8, budget // args.gpus)))
     return subprocess.call(cmd, env=env)

@@ -70,7 +70,8 @@ def workload_text(wl):
               "random-init weights (counter-based generator, seed 0)" + (f" [{cfg}]" if cfg else ""))
 
 
-def assemble(wl, dt, res, roof, cpu, cpu_hf, side):
+def assemble(wl, dt, res, roof=None, cpu=None, cpu_hf=None, side=None):
+    """side is None: a plain run, whose line carries no roofline, CPU baseline or side measurement (--full measures them)."""
     a, world = wl.args, wl.world
     dtype = "bf16"
     if a.fp8:
@@ -91,7 +92,11 @@ def assemble(wl, dt, res, roof, cpu, cpu_hf, side):
                    "decode": "hipGraph" if not a.no_graph else "eager", "exchange": exchange_report(a, world)},
         "roofline": roof, "cpu_baseline": cpu, "cpu_baseline_torch_bf16": cpu_hf, "phase_ms_per_step": phases(wl),
     }
-    out.update(side)
+    if side is None:
+        for k in ("roofline", "cpu_baseline", "cpu_baseline_torch_bf16"):
+            del out[k]
+    else:
+        out.update(side)
     out.update({"weights_load_s": round(wl.load_s, 1), "workspace_GB": round(wl.eng.workspace_bytes / 1e9, 2),
                 "result_checksum": int(res.sum().item()),
                 # one per tile of the last step, in tile order over all ranks

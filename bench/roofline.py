@@ -108,7 +108,7 @@ def measure_gemv_in_situ(args, B, steps=1):
     """The decode weight stream timed where it runs: a rocprofv3 kernel trace of `bench.py --static --batch B` (this script, one static batch per
     step, hipGraph-replayed decode, nothing else) as a child process.  Returns {"avg_us": launch-count-weighted average duration of every k_gemv*
     dispatch, "launches": n, "per_kernel_avg_us": {...}, "other_decode_kernels_avg_us": {...}} or None (no rocprofv3 / a failed pass)."""
-    cmd = [PYTHON, os.path.join(ROOT, "bench.py"), "--static", "--batch", str(B), "--steps", str(steps), "--warmup", "1", "--no-latency",
+    cmd = [PYTHON, os.path.join(ROOT, "bench.py"), "--full", "--static", "--batch", str(B), "--steps", str(steps), "--warmup", "1", "--no-latency",
            "--no-cpu-baseline", "--no-pmc", "--tile", str(args.tile)]
     cmd += (["--fp8-mx"] if args.fp8_mx else ["--fp8"] if args.fp8 else []) + (["--pair"] if args.pair else [])
     db, td = _rocprof(cmd)

@@ -45,7 +45,7 @@ def more_rows():
     run as a child process (own engine, 2 steps of 2 x rows requests, no side measurements)."""
     out = {}
     for rows_ in (64, 128):
-        cmd = [PYTHON, os.path.join(ROOT, "bench.py"), "--batch", str(rows_), "--steps", "2", "--warmup", "1", "--waves", "2", "--no-latency",
+        cmd = [PYTHON, os.path.join(ROOT, "bench.py"), "--full", "--batch", str(rows_), "--steps", "2", "--warmup", "1", "--waves", "2", "--no-latency",
                "--no-cpu-baseline", "--no-pmc"]
         try:
             j_ = last_json_line(subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=child_env()).stdout)

@@ -7,12 +7,22 @@ Nothing is skipped inside a step; the per-tile result row (128 tokens + 2 IoU co
 """
 from __future__ import annotations
 
+import os
 import time
 
 import numpy as np
 import torch
 
 from .common import N_NEW, RAGGED_HI
+
+
+def dump_outputs(res, out_dir):
+    """What a step hands its caller, for the tiles of `res` (the per-tile result rows of one step, all ranks, tile order): the greedy tokens
+    [n, 128] and the (intersection, union) IoU counts [n, 2], as float64 .npy files (integers below 2^53: exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    r = res.cpu().numpy()
+    np.save(os.path.join(out_dir, "tokens.npy"), r[:, :N_NEW].astype(np.float64))
+    np.save(os.path.join(out_dir, "iou_counts.npy"), r[:, N_NEW:].astype(np.float64))
 
 
 class Workload:

@@ -403,7 +403,7 @@ def test_two_rank_data_parallel_bench_equals_single_process():
         assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
         line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
         return json.loads(line)
-    common = ["--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    common = ["--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]      # (--full: the roofline object checked below)
     tr = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1"]
     one = run([sys.executable, "bench.py", "--batch", "2", "--static", "--no-latency"] + common)
     two = run(tr + ["--master-port", "29551", "bench.py", "--gpus", "2", "--batch", "1"] + common)

@@ -38,7 +38,7 @@ R=$PWD
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 RT=${RT:-r06}      # round tag of every output file (profiles/r06_*)
-QUIET="--no-cpu-baseline --no-latency --no-sam --no-more-rows"
+QUIET="--full --no-cpu-baseline --no-latency --no-sam --no-more-rows"      # (--full: the roofline object and the static-batch figures line() prints)
 
 line() { python - "$1" "$2" <<'EOF'
 import json, sys
@@ -73,7 +73,7 @@ for stage in "$@"; do
         SR_GEMV_XLDS=$v timeout 600 python bench.py --static --steps 3 --warmup 1 $QUIET --no-pmc > gpurun_out/${RT}_xl_s32_$v.log 2>&1; line gpurun_out/${RT}_xl_s32_$v.log "static 32 SR_GEMV_XLDS=$v rep $rep:"
       done; done | tee gpurun_out/${RT}_gemv_xlds_ab.txt ;;
     counted_ab) for rep in 1 2; do for v in 0 1; do
-        SR_GEMV_COUNTED=$v timeout 600 python bench.py --batch 1 --steps 3 --warmup 1 --no-cpu-baseline --no-sam --no-pmc > gpurun_out/${RT}_cnt_b1_$v.log 2>&1; line gpurun_out/${RT}_cnt_b1_$v.log "batch 1 SR_GEMV_COUNTED=$v rep $rep:"
+        line <(SR_GEMV_COUNTED=$v timeout 600 python bench.py --full --batch 1 --steps 3 --warmup 1 --no-cpu-baseline --no-sam --no-pmc) "batch 1 SR_GEMV_COUNTED=$v rep $rep:"
         SR_GEMV_COUNTED=$v timeout 600 python bench.py --static --steps 3 --warmup 1 $QUIET --no-pmc > gpurun_out/${RT}_cnt_s32_$v.log 2>&1; line gpurun_out/${RT}_cnt_s32_$v.log "static 32 SR_GEMV_COUNTED=$v rep $rep:"
       done; done | tee gpurun_out/${RT}_gemv_counted_ab.txt ;;
     masked_trace|masked_trace_px)      # (masked_trace: the streaming GEMVs on every stream; masked_trace_px: the scheduler's CU hint on the masked ones -> the x-stationary GEMVs)
@@ -104,8 +104,8 @@ except Exception as e:
     trace_sam2) rm -rf /tmp/prof_${RT}_sam; (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_${RT}_sam -o sam -- python $R/tools/prof_sam2_encoder.py f32 > $R/gpurun_out/${RT}_prof_sam2.log 2>&1; echo "trace sam2 exit $?")
                 DB=$(find /tmp/prof_${RT}_sam -name "sam_results.db" | head -1); [ -n "$DB" ] && python tools/rocpd_stats.py $DB gpurun_out/${RT}_sam2_f32_encoder_kernel_stats.md > /dev/null && head -20 gpurun_out/${RT}_sam2_f32_encoder_kernel_stats.md | cut -c1-170
                 [ -n "$DB" ] && python tools/rocpd_by_grid.py $DB gpurun_out/${RT}_sam2_f32_by_grid.md 30 > /dev/null 2>&1 && head -36 gpurun_out/${RT}_sam2_f32_by_grid.md | cut -c1-200 ;;
-    bench_pmc) timeout 900 python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-sam --no-more-rows --no-pipeline > gpurun_out/${RT}_bench_pmc.log 2> gpurun_out/${RT}_bench_pmc.err; python -c "
-import json; d=json.loads([l for l in open('gpurun_out/${RT}_bench_pmc.log') if l.startswith('{')][-1]); r=d['roofline']; print({k: r[k] for k in ('frac','traffic','traffic_over_algorithmic','bytes_per_launch')}); print(r['traffic_source'][:160]); print(d['latency_b1']['roofline'])" ;;
+    bench_pmc) timeout 900 python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-sam --no-more-rows --no-pipeline | python -c "
+import json, sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r=d['roofline']; print({k: r[k] for k in ('frac','traffic','traffic_over_algorithmic','bytes_per_launch')}); print(r['traffic_source'][:160]); print(d['latency_b1']['roofline'])" ;;
     host_scaling) : > gpurun_out/${RT}_host_scaling.jsonl
       for n in 1 2 4 8; do
         SR_DIST_BACKEND=gloo timeout 900 python bench.py --gpus $n --batch 8 --waves 2 --steps 2 --warmup 1 --no-cpu-baseline --no-latency --no-sam --no-more-rows > gpurun_out/${RT}_hs.log 2> gpurun_out/${RT}_hs.err
@@ -134,7 +134,7 @@ PY
     smoke)  timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 ;;
     trace_s32) trace s32 --static --steps 2 --warmup 1 $QUIET ;;
     trace_c32) trace c32 --steps 2 --warmup 1 $QUIET ;;
-    trace_b1)  trace b1 --batch 1 --steps 3 --warmup 1 --no-cpu-baseline --no-sam ;;
+    trace_b1)  trace b1 --full --batch 1 --steps 3 --warmup 1 --no-cpu-baseline --no-sam ;;
     trace_fp8) trace fp8_s32 --fp8 --static --steps 2 --warmup 1 $QUIET ;;
     attn_ab)   # prefill attention with the V^T reads issued by hand (default) / left to the compiler, kernel trace of tools/probe_attn.py, twice each
       for rep in 1 2; do for v in 0 1; do rm -rf /tmp/attn_ab
