@@ -195,6 +195,22 @@ int sr_admit_stage(sr_engine* e, const int64_t* host_ids, const int64_t* host_po
                    const int32_t* host_kv_slots, const int32_t* host_max_new, int n, const void* dev_image_embeds, int n_image_rows,
                    float* dev_logits_out, void* stream);
 int sr_admit_commit(sr_engine* e, const int32_t* host_rows, int n, void* stream);
+/* Fan-out admission (the reference's num_return_sequences n > 1 -- vLLM serves it from one prefill whose KV blocks the n sequences share):
+ * n PROMPTS, prompt i becomes host_fanout[i] >= 1 staged sequences, in prompt-major order; host_kv_slots (sr_admit_fanout: host_rows, slot ==
+ * row) holds one entry per sequence (sum of host_fanout), sequence j of prompt i takes the j-th of prompt i's entries.  Prompt i is prefilled
+ * ONCE, into the slot of its first sequence; the LM head runs once per prompt (dev_logits_out, optional: n rows); one k_kv_fanout launch on
+ * `stream` copies every prompt's KV prefix (positions [0, len) of all layers) into the slots of its other sequences before the call returns.
+ * Each sequence gets its own first token: the prompt's arg-max (greedy) or its own k_sample draw from the prompt's logits row (sampling mode,
+ * the sequence's staged index picks the random stream).  host_max_new has n entries (per prompt).  sr_admit_commit installs the sequences
+ * unchanged, in portions as rows free up: the forks of one prompt may start at different steps.  Refused, with the value named: a fanout
+ * below 1, more than MAXB (128) sequences in one admission, a slot or row given twice or out of range.  sr_admit_stage / sr_admit are
+ * these calls with every fanout 1 (the same code path, no k_kv_fanout launch). */
+int sr_admit_stage_fanout(sr_engine* e, const int64_t* host_ids, const int64_t* host_pos3, const int32_t* host_seq_lens,
+                          const int32_t* host_fanout, const int32_t* host_kv_slots, const int32_t* host_max_new, int n,
+                          const void* dev_image_embeds, int n_image_rows, float* dev_logits_out, void* stream);
+int sr_admit_fanout(sr_engine* e, const int64_t* host_ids, const int64_t* host_pos3, const int32_t* host_seq_lens,
+                    const int32_t* host_fanout, const int32_t* host_rows, const int32_t* host_max_new, int n,
+                    const void* dev_image_embeds, int n_image_rows, float* dev_logits_out, void* stream);
 int sr_rows_step(sr_engine* e, int n_steps, const int32_t* host_eos, int n_eos, int32_t pad_id, void* stream);
 int sr_rows_poll(sr_engine* e, int32_t* host_finished, int32_t* host_steps, void* stream);
 int sr_rows_read(sr_engine* e, int row, int32_t* dev_tokens_out, int n, void* stream);
@@ -309,6 +325,11 @@ int sr_op_rmsnorm(const void* x, const void* w, void* out, int rows, int H, floa
 int sr_op_resid_rmsnorm(void* x, const float* partials, int ksplit, const void* w, void* out, int rows, int H, float eps,
                         void* stream);
 int sr_op_argmax(const float* logits, int rows, int V, int32_t* out_idx, void* stream);
+/* the fan-out kernel of sr_admit_stage_fanout on caller-provided caches kcache [layer][slot][kvh][max_ctx][128], vtcache
+ * [layer][slot][kvh][128][max_ctx] (layer_stride_elems elements from one layer to the next in each): positions [0, L) of slot src_slot ->
+ * slots dev_dst_slots[0..d) (int32, device), all layers, one launch; nothing else is written.  max_ctx % 64 == 0. */
+int sr_op_kv_fanout(void* kcache, void* vtcache, int n_layers, int64_t layer_stride_elems, int n_kv_heads, int max_ctx, int src_slot,
+                    const int32_t* dev_dst_slots, int d, int L, void* stream);
 /* the sampling kernel on caller-provided float32 logits [B, V]; dev_seen: optional bitmask [B][(V+31)/32]; dev_step: optional
  * int32 [B]; dev_blk_max: optional per-block maxima [B][n_blk] of blk_rows consecutive ids each (the LM head's argmax partials):
  * the exact top-k is then searched only in the blocks that can contain it */

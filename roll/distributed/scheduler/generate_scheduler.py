@@ -6,13 +6,16 @@ batch (socioreasoner_amd.dp): level 0 is one ``generate`` call on the local work
 single-prompt requests and -- with more than one rank -- deals them out ACROSS the ranks like the reference does
 (least requests in flight first, ``max_running_requests`` per worker, reference :57, 180-187), each rank's request loop
 serving what it is handed and every rank getting the answers of its own prompts back in prompt order
-(socioreasoner_amd/dispatch.py); with one rank the local request loop serves them all."""
+(socioreasoner_amd/dispatch.py); with one rank the local request loop serves them all.
+
+num_return_sequences n > 1 travels to the worker at both levels (a prompt is admitted once and fanned out into n sequences by the
+engine); the output has n rows per prompt, prompt-major with a prompt's rows adjacent -- the layout of the reference's
+is_num_return_sequences_expand (reference :103-140), which therefore no longer copies prompts."""
 from __future__ import annotations
 
 import threading
 from typing import Dict, List
 
-import numpy as np
 import torch
 
 from roll.distributed.scheduler.protocol import DataProto
@@ -20,21 +23,12 @@ from roll.utils.functionals import GenerateRequestType
 from socioreasoner_amd import hostops
 
 
-def expand_num_return_sequences(data: DataProto, n: int) -> DataProto:
-    """Repeat every prompt n times, neighbours adjacent (reference :103-140)."""
-    if n == 1:
-        return data
-    batch = {k: v.repeat_interleave(n, dim=0) for k, v in data.batch.items()}
-    nt = {k: np.repeat(v, n) for k, v in data.non_tensor_batch.items()}
-    return DataProto(batch=batch, non_tensor_batch=nt, meta_info=dict(data.meta_info))
-
-
 class GenerateScheduler:
     max_running_requests = 128          # per worker (reference :57)
 
     def __init__(self):
         self.lock = threading.Lock()
-        self.results: Dict[int, List[int]] = {}
+        self.results: Dict[int, List[List[int]]] = {}      # request id -> its n token lists
         self.done = threading.Event()
         self.round = 0                  # generate calls so far: every rank counts them alike, keys of different calls never meet
         self.sink = None                # cross-rank mode: where finished requests are reported
@@ -42,10 +36,10 @@ class GenerateScheduler:
 
     def report_response(self, data: DataProto):
         if self.sink is not None:       # cross-rank dispatch: the request may belong to another rank
-            self.sink(int(data.meta_info["request_id"]), data.meta_info["output_token_ids"][0])
+            self.sink(int(data.meta_info["request_id"]), [list(t) for t in data.meta_info["output_token_ids"]])
             return
         with self.lock:
-            self.results[int(data.meta_info["request_id"])] = data.meta_info["output_token_ids"][0]
+            self.results[int(data.meta_info["request_id"])] = [list(t) for t in data.meta_info["output_token_ids"]]
             if len(self.results) == self.expected:
                 self.done.set()
 
@@ -53,16 +47,15 @@ class GenerateScheduler:
         worker = actor_cluster
         ga = dict(worker.worker_config.generating_args or {})
         n = int(ga.get("num_return_sequences", 1) or 1)
-        expand = bool(pipeline_config.get("is_num_return_sequences_expand"))
+        # (is_num_return_sequences_expand changes nothing here: the worker serves n sequences per prompt from one admission, and the
+        # output rows come prompt-major with a prompt's n rows adjacent, the expanded layout)
         gc = dict(ga)
-        gc["num_return_sequences"] = 1 if expand else n
+        gc["num_return_sequences"] = n
         gc.setdefault("max_new_tokens", int(pipeline_config.response_length))
         data.meta_info["generation_config"] = gc
         data.batch["prompt_id"] = torch.arange(len(data))
         level = int(pipeline_config.get("generate_opt_level") or 0)
         if level == 0:
-            if expand:
-                data = expand_num_return_sequences(data, n)
             out = worker.generate(data)
             out.meta_info.setdefault("metrics", {})
             return out
@@ -76,7 +69,8 @@ class GenerateScheduler:
         import torch.distributed as dist
         if int(pipeline_config.get("generate_opt_level") or 0) < 1 or not dist.is_initialized() or dist.get_world_size() == 1:
             return
-        self._generate_requests(None, actor_cluster, {}, pipeline_config)
+        n = int((actor_cluster.worker_config.generating_args or {}).get("num_return_sequences", 1) or 1)
+        self._generate_requests(None, actor_cluster, {"num_return_sequences": n}, pipeline_config)     # (the dispatcher counts n sequences per request)
 
     def _generate_requests(self, data, worker, gc, pipeline_config) -> DataProto:
         import time
@@ -85,7 +79,8 @@ class GenerateScheduler:
         self.round += 1
         reqs = [] if data is None else [DataProto(batch={k: v[i:i + 1] for k, v in data.batch.items()},
                           non_tensor_batch={k: v[i:i + 1] for k, v in data.non_tensor_batch.items()},
-                          meta_info={"request_id": i, "generation_config": dict(gc, num_return_sequences=1)}) for i in range(B)]
+                          meta_info={"request_id": i, "generation_config": dict(gc)}) for i in range(B)]
+        n = int(gc.get("num_return_sequences", 1) or 1)
         timeout = float(pipeline_config.get("rpc_timeout") or 3600)
         world = dist.get_world_size() if dist.is_initialized() else 1
         worker.start_server(DataProto(meta_info={}), request_complete_callback=self.report_response)
@@ -93,7 +88,8 @@ class GenerateScheduler:
             # request-level dispatch over all ranks (reference generate_opt_level_1): collective -- every rank is in this call
             from socioreasoner_amd.dispatch import CrossRankDispatcher, default_store
             cap = int(pipeline_config.get("max_running_requests") or self.max_running_requests)
-            disp = CrossRankDispatcher(default_store(), dist.get_rank(), world, self.round, max_running_requests=cap, timeout_s=timeout)
+            disp = CrossRankDispatcher(default_store(), dist.get_rank(), world, self.round, max_running_requests=cap, timeout_s=timeout,
+                                       num_return_sequences=n)
             try:
                 got = disp.run(reqs, add_request=lambda r: worker.add_request(GenerateRequestType.ADD, r),
                                make_result_sink=lambda cb: setattr(self, "sink", cb),
@@ -118,8 +114,8 @@ class GenerateScheduler:
                     worker.stop_server()
                     raise TimeoutError(f"{B - len(self.results)} of {B} generation requests did not complete")
             worker.stop_server()
-        rows = [self.results[i] for i in range(B)]                      # re-sorted by prompt id (reference :293-294)
-        return assemble_responses(data, rows, worker, pipeline_config)
+        rows = [t for i in range(B) for t in self.results[i]]           # re-sorted by prompt id (reference :293-294), a prompt's n answers adjacent
+        return assemble_responses(data, rows, worker, pipeline_config, n)
 
     def open_stream(self, actor_cluster, pipeline_config) -> "RequestStream":
         """The request loop of level 1 kept OPEN across several batches of prompts (round 6; no reference counterpart -- the reference's two stages are
@@ -133,12 +129,14 @@ class GenerateScheduler:
         return RequestStream(worker, gc, float(pipeline_config.get("rpc_timeout") or 3600))
 
 
-def assemble_responses(data: DataProto, rows: List[List[int]], worker, pipeline_config) -> DataProto:
-    """token lists of the prompts of `data` (in its row order) -> the reference's 7 output tensors (postprocess_generate, reference :293-334)"""
+def assemble_responses(data: DataProto, rows: List[List[int]], worker, pipeline_config, n: int = 1) -> DataProto:
+    """token lists of the prompts of `data` (in its row order; n per prompt, adjacent) -> the reference's 7 output tensors (postprocess_generate,
+    reference :293-334)"""
     pad = worker.tokenizer.pad_token_id
+    assert len(rows) == n * len(data), (len(rows), n, len(data))
     output_ids = hostops.gather_outputs_to_pad_tensor(rows, pad, device=data.batch["input_ids"].device)
-    seq = hostops.concatenate_input_and_output(data.batch["input_ids"], output_ids, 1)
-    out = hostops.postprocess_generate(prompts=data.batch, output=seq, num_return_sequences=1,
+    seq = hostops.concatenate_input_and_output(data.batch["input_ids"], output_ids, n)
+    out = hostops.postprocess_generate(prompts=data.batch, output=seq, num_return_sequences=n,
                                        sequence_length=int(pipeline_config.sequence_length),
                                        eos_token_id=worker.tokenizer.eos_token_id, pad_token_id=pad)
     return DataProto(batch=out, meta_info={"metrics": {}})

@@ -331,33 +331,44 @@ class Mi355xStrategy(InferenceStrategy):
         tk = -1 if tk is None else int(tk)
         on_device = not greedy and tk <= 1024 and float(gc.get("temperature", 1.0)) > 1e-5
         rp1 = float(gc.get("repetition_penalty", 1.0) or 1.0) == 1.0
-        if greedy or (on_device and rp1 and n == 1):
+        if greedy or (on_device and rp1):
             # the stages are decoupled: the scheduler admits the prompts in capacity-sized groups (ViT + prefill into free KV rows)
             # and ALL filled rows decode together -- a batch larger than one admission, or than max_batch, still decodes at full
-            # width, and rows freed by short answers are refilled at once (socioreasoner_amd/serving.py)
+            # width, and rows freed by short answers are refilled at once (socioreasoner_amd/serving.py).  Sampled n > 1: one request of n
+            # sequences per prompt (chunks of at most max_batch), prefilled once and fanned out into n rows by the engine
             from socioreasoner_amd.serving import ContinuousBatcher, Request
             smp = None if greedy else {"temperature": float(gc.get("temperature", 1.0)), "top_k": int(tk), "top_p": float(gc.get("top_p", 1.0) or 1.0),
                                        "seed": int(gc.get("seed", 0) or 0) * 1000003 + 7919 * int(getattr(self.worker, "rank", 0) or 0)}
-            reqs = []
+            reqs, owner = [], []
+            fan = 1 if greedy else n                   # greedy n > 1: the n answers are one answer, copied below
+            mb = self.engine.cfg.max_batch
             for k in range(B):
                 ids_k, pos_k, ims_k, grids_k = prepared[k]
                 room = self.engine.cfg.max_ctx - len(ids_k)
                 if room < 1:
                     raise ValueError(f"prompt of {len(ids_k)} tokens leaves no room in max_ctx {self.engine.cfg.max_ctx}")
-                reqs.append(Request(ids=ids_k, pos3=pos_k, max_new=max(1, min(max_new, room)), images=ims_k, grids=grids_k))
+                for c0 in range(0, fan, mb):
+                    reqs.append(Request(ids=ids_k, pos3=pos_k, max_new=max(1, min(max_new, room)), images=ims_k, grids=grids_k, n=min(mb, fan - c0)))
+                    owner.append(k)
             t_run0 = _time.perf_counter()
             cb = ContinuousBatcher(self.engine, eos, pad, sampling=smp, overlap=self.overlap)
             outs = cb.run(reqs)
             # where a generate call's wall time went (tools/run_example_small.py prints it): host preparation of the requests, then the scheduler's run
             self.gen_stats.append({"requests": B, "prepare_s": round(t_run0 - t_gen0, 3), "run_s": round(_time.perf_counter() - t_run0, 3),
                                    **{k: (round(v, 1) if isinstance(v, float) else v) for k, v in cb.stats.items()
-                                      if k in ("steps", "steps_shared", "admissions", "rounds", "host_ms", "poll_wait_ms", "shares", "share_model")}})
+                                      if k in ("admitted", "admitted_prompts", "steps", "steps_shared", "admissions", "rounds", "host_ms",
+                                               "poll_wait_ms", "shares", "share_model")}})
             for k in range(B):
-                row = [int(t) for t in outs[k]]
-                cut = next((j + 1 for j, t in enumerate(row) if t in eos), len(row))
-                results[k] = [row[:cut]] * n
+                results[k] = []
+            for k, r, out in zip(owner, reqs, outs):
+                for row in (out if r.n > 1 else [out]):
+                    row = [int(t) for t in row]
+                    cut = next((j + 1 for j, t in enumerate(row) if t in eos), len(row))
+                    results[k].append(row[:cut])
+            if greedy:
+                results = [rs * n for rs in results]
             i = B
-        while i < B:                                  # static batches (repetition penalty, unbounded top-k, n > 1 sampled sequences)
+        while i < B:                                  # static batches (repetition penalty, top-k above 1024)
             grp, ntok, npatch = [], 0, 0
             while i < B and len(grp) < self.max_batch:
                 ids_i, _, _, grids = prepared[i]
@@ -443,9 +454,10 @@ class Mi355xStrategy(InferenceStrategy):
     def start_server(self, data: DataProto, request_complete_callback):
         """Request-level serving (reference vllm_strategy.py:156-205): ADD / ABORT / STOP commands arrive through the queue
         while the loop runs; greedy requests and sampling requests with a top-k bound are served by CONTINUOUS batching
-        (socioreasoner_amd.serving: admit on finish, one graph replay per token for all rows, the draw inside the graph);
-        anything else (unbounded top-k, repetition penalty, n > 1) in engine-sized static batches.  Each request is reported
-        through the callback the moment its sequence ends."""
+        (socioreasoner_amd.serving: admit on finish, one graph replay per token for all rows, the draw inside the graph; a sampled request
+        with num_return_sequences n > 1 is admitted once and fanned out into n rows); anything else (repetition penalty, top-k above 1024,
+        n above the engine's rows) in engine-sized static batches.  Each request is reported through the callback the moment its last
+        sequence ends, with its n token lists in output_token_ids."""
         from socioreasoner_amd.serving import ContinuousBatcher, Request
         self.running = True
         batcher, bkey = None, None
@@ -471,7 +483,9 @@ class Mi355xStrategy(InferenceStrategy):
                     tk = gc.get("top_k", -1)
                     tk = -1 if tk is None else int(tk)
                     dev_sampling = not greedy and tk <= 1024 and float(gc.get("temperature", 1.0)) > 1e-5
-                    rows_ok = hasattr(self.engine, "rows_begin") and rp1 and (greedy or dev_sampling) and int(gc.get("num_return_sequences", 1) or 1) == 1
+                    n_req = int(gc.get("num_return_sequences", 1) or 1)
+                    rows_ok = (hasattr(self.engine, "rows_begin") and rp1 and (greedy or dev_sampling)
+                               and n_req <= getattr(getattr(self.engine, "cfg", None), "max_batch", 1))
                     if not rows_ok:
                         sampled.append(req)
                     else:
@@ -500,7 +514,8 @@ class Mi355xStrategy(InferenceStrategy):
                             if room < 1:
                                 raise ValueError(f"prompt of {len(ids)} tokens leaves no room in max_ctx {self.engine.cfg.max_ctx}")
                             max_new = max(1, min(int(gc["max_new_tokens"]), self.engine.cfg.max_new_tokens, room))
-                            batcher.submit(Request(ids=ids, pos3=pos3, max_new=max_new, images=ims, grids=grids, tag=req))
+                            batcher.submit(Request(ids=ids, pos3=pos3, max_new=max_new, images=ims, grids=grids, tag=req,
+                                                   n=1 if greedy else n_req))          # (greedy: the n answers are one answer)
                 elif name == "ABORT":
                     rid = req.meta_info["request_id"]
                     sampled = [p for p in sampled if p.meta_info.get("request_id") != rid]
@@ -525,7 +540,9 @@ class Mi355xStrategy(InferenceStrategy):
                     if r.aborted:
                         return
                     res = DataProto(meta_info=dict(r.tag.meta_info))
-                    res.meta_info["output_token_ids"] = [[int(t) for t in toks]]
+                    n_out = int((r.tag.meta_info.get("generation_config") or {}).get("num_return_sequences", 1) or 1)
+                    lists = toks if r.n > 1 else [toks] * n_out
+                    res.meta_info["output_token_ids"] = [[int(t) for t in x] for x in lists]
                     request_complete_callback(data=res)
                 batcher.pump(done)
             if sampled and (len(sampled) >= self.max_batch or self.command_queue.empty()):
@@ -538,9 +555,11 @@ class Mi355xStrategy(InferenceStrategy):
                     out = self.generate(merged, gc)
                     batcher = None                # generate() re-initialises the batch rows
                     P = merged.batch["input_ids"].shape[1]
-                    for row, r in zip(out, todo):
+                    n_out = int(gc.get("num_return_sequences", 1) or 1)
+                    for i_r, r in enumerate(todo):         # n rows per request, adjacent
                         res = DataProto(meta_info=dict(r.meta_info))
-                        res.meta_info["output_token_ids"] = [[int(t) for t in row[P:].tolist() if int(t) != int(gc.get("pad_token_id", -1))]]
+                        res.meta_info["output_token_ids"] = [[int(t) for t in row[P:].tolist() if int(t) != int(gc.get("pad_token_id", -1))]
+                                                             for row in out[i_r * n_out:(i_r + 1) * n_out]]
                         request_complete_callback(data=res)
             if stop and (batcher is None or batcher.idle()) and not sampled:
                 self.running = False

@@ -212,10 +212,10 @@ __global__ __launch_bounds__(256) void k_f32_to_bf16_pad(const float* in, int co
 
 // ----------------------------------------------------------------------------------------------- greedy argmax
 // lowest index among the maxima (torch.argmax on the reference's CPU path)
-__global__ __launch_bounds__(1024) void k_argmax(const float* logits, int V, int* out_idx) {
+__global__ __launch_bounds__(1024) void k_argmax(const float* logits, int V, int* out_idx, const int* row_map) {
     __shared__ float sv[16];
     __shared__ int si[16];
-    const float* row = logits + (size_t)blockIdx.x * V;
+    const float* row = logits + (size_t)(row_map ? row_map[blockIdx.x] : blockIdx.x) * V;
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = threadIdx.x; i < V; i += blockDim.x) {
@@ -553,9 +553,9 @@ int launch_f32_to_bf16_pad(hipStream_t s, const float* in, int rows, int cols, b
     SR_CHECK_LAUNCH();
     return 0;
 }
-int launch_argmax(hipStream_t s, const float* logits, int rows, int V, int* out_idx) {
+int launch_argmax(hipStream_t s, const float* logits, int rows, int V, int* out_idx, const int* row_map) {
     if (rows <= 0) return 0;
-    hipLaunchKernelGGL(k_argmax, dim3(rows), dim3(1024), 0, s, logits, V, out_idx);
+    hipLaunchKernelGGL(k_argmax, dim3(rows), dim3(1024), 0, s, logits, V, out_idx, row_map);
     SR_CHECK_LAUNCH();
     return 0;
 }

@@ -143,6 +143,7 @@ struct sr_engine {
     // continuous batching (sr_rows_*): admission scratch so that a prefill never touches the pending tokens of running rows
     float *d_logits_adm = nullptr, *d_amax_val_adm = nullptr;
     int *d_amax_idx_adm = nullptr, *d_row_limit = nullptr, *d_ngen = nullptr, *d_adm = nullptr;   // d_adm: [rows | ctx | pos | limit | first_tok] x MAXB
+    int* d_fan = nullptr;          // fan-out admission: [prompt of each staged sequence] x MAXB | [src slot | L | first fork index | forks - 1] x MAXB
     bool rows_mode = false;
     bool finalized = false;        // sr_finalize_weights ran (fp8 mode: the LM linears are quantised)
     bf16_t *kcache, *vtcache;
@@ -376,8 +377,9 @@ void carve(sr_engine* e) {
 
     // control staging: ViT needs NP*(8 + 4*hd) + work lists; prefill needs ~24 B per token + work lists
     e->stage_bytes = NP * (8 + 4 * (size_t)e->v_hd) + (NP / 4 + NP / 64 + NP / 128 + 192) * sizeof(AttnWork) + TP * 28 +
-                     (TP / 64 + 64) * sizeof(AttnWork) + 4096 + 5 * MAXB * sizeof(int);
+                     (TP / 64 + 64) * sizeof(AttnWork) + 4096 + 10 * MAXB * sizeof(int);
     e->d_stage = ar.take<char>(e->stage_bytes);
+    e->d_fan = ar.take<int>(5 * MAXB);
 }
 
 void register_expected(sr_engine* e) {
@@ -1007,10 +1009,13 @@ static int commit_admission(sr_engine* e, const int32_t* rows, int n, hipStream_
     return 0;
 }
 
-// `commit`: admission only -- install the rows right away (rows = slots: the plain sr_admit); false = stage, sr_admit_commit installs later
+// `commit`: admission only -- install the rows right away (rows = slots: the plain sr_admit); false = stage, sr_admit_commit installs later.
+// Admission only, `fanout` / `fork_slots` (both null: one sequence per prompt): prompt b becomes fanout[b] staged sequences (prompt-major) whose
+// KV slots are fork_slots (sum of fanout entries); it is prefilled once into slots[b] (= its first fork's slot), its LM head runs once, and
+// one k_kv_fanout launch copies every prompt's prefix into the slots of its other forks.  Each staged sequence draws its own first token.
 static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* slots, int B,
                         const void* image_embeds, int n_image_rows, float* logits_out, void* stream, const int32_t* limits,
-                        float* all_logits_out = nullptr, bool commit = true) {
+                        float* all_logits_out = nullptr, bool commit = true, const int32_t* fanout = nullptr, const int32_t* fork_slots = nullptr) {
     enter(e);
     if (!e || !ids || !pos3 || !seq_lens || !slots) return fail(e, -22, "sr_prefill: null argument");
     char miss[160];
@@ -1035,10 +1040,12 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
     int* h_slot = h_pos + 3 * n_tok;
     int* h_idx = h_slot + n_tok;
     int* h_last = h_idx + n_tok;
-    int* h_state = h_last + MAXB;           // [ctx_len | pos | slots | limit] x MAXB
+    int* h_state = h_last + MAXB;           // [ctx_len | pos | slots | limit] x MAXB, per staged sequence
     for (int i = 0; i < 4 * MAXB; ++i) h_state[i] = 0;
-    AttnWork* h_work = reinterpret_cast<AttnWork*>(((uintptr_t)(h_state + 4 * MAXB) + 15) & ~(uintptr_t)15);
-    int n_work = 0, img_row = 0, t0 = 0;
+    int* h_map = h_state + 4 * MAXB;        // fan-out (d_fan): prompt of each staged sequence, then [src slot | L | first fork index | forks - 1] per group
+    int* h_grp = h_map + MAXB;
+    AttnWork* h_work = reinterpret_cast<AttnWork*>(((uintptr_t)(h_grp + 4 * MAXB) + 15) & ~(uintptr_t)15);
+    int n_work = 0, img_row = 0, t0 = 0, n_seq = 0, n_groups = 0, max_L = 0;
     const int KVH = c.t_kv_heads;
     for (int b = 0; b < B; ++b) {
         const int S = seq_lens[b];
@@ -1061,11 +1068,20 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
         for (int q0 = 0; q0 < S; q0 += 64)
             h_work[n_work++] = AttnWork{t0 + q0, S, q0, slots[b] * KVH * c.max_ctx, (long long)slots[b] * KVH * 128 * c.max_ctx};
         h_last[b] = t0 + S - 1;
-        h_state[b] = S;                     // keys in the cache; k_step_advance adds the new token before each forward
-        h_state[MAXB + b] = (int)maxpos;      // decode positions continue at max+1 on all three axes
-                                            // (reference rule: roll/utils/functionals.py:816-818)
-        h_state[2 * MAXB + b] = slots[b];
-        h_state[3 * MAXB + b] = limits ? limits[b] : 0x7f7f7f7f;
+        const int f = fanout ? fanout[b] : 1;
+        if (f > 1) {
+            int* g = h_grp + 4 * n_groups++;
+            g[0] = slots[b]; g[1] = S; g[2] = n_seq + 1; g[3] = f - 1;
+            max_L = std::max(max_L, S);
+        }
+        for (int j = 0; j < f; ++j, ++n_seq) {
+            h_map[n_seq] = b;
+            h_state[n_seq] = S;                     // keys in the cache; k_step_advance adds the new token before each forward
+            h_state[MAXB + n_seq] = (int)maxpos;      // decode positions continue at max+1 on all three axes
+                                                    // (reference rule: roll/utils/functionals.py:816-818)
+            h_state[2 * MAXB + n_seq] = fork_slots ? fork_slots[n_seq] : slots[b];
+            h_state[3 * MAXB + n_seq] = limits ? limits[b] : 0x7f7f7f7f;
+        }
         t0 += S;
     }
     if (image_embeds && img_row != n_image_rows)
@@ -1093,6 +1109,7 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
         SR_TRY((int)hipMemcpyAsync(e->d_adm + MAXB, dmirror(h_state), MAXB * 4, hipMemcpyDeviceToDevice, s));
         SR_TRY((int)hipMemcpyAsync(e->d_adm + 2 * MAXB, dmirror(h_state + MAXB), MAXB * 4, hipMemcpyDeviceToDevice, s));
         SR_TRY((int)hipMemcpyAsync(e->d_adm + 3 * MAXB, dmirror(h_state + 3 * MAXB), MAXB * 4, hipMemcpyDeviceToDevice, s));
+        if (n_groups) SR_TRY((int)hipMemcpyAsync(e->d_fan, dmirror(h_map), 5 * MAXB * 4, hipMemcpyDeviceToDevice, s));
     }
 
     // ---- forward over the packed tokens
@@ -1166,15 +1183,22 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
         SR_TRY(launch_gemv(s, g, GV_F32));
     }
     if (logits_out) SR_TRY((int)hipMemcpyAsync(logits_out, e->d_logits_adm, (size_t)B * c.t_vocab * 4, hipMemcpyDeviceToDevice, s));
-    SR_TRY(launch_argmax(s, e->d_logits_adm, B, c.t_vocab, e->d_adm + 4 * MAXB));
+    // first token of every staged sequence: the forks of a prompt read its logits row (row map), each draws at its own staged index
+    const int* row_map = n_groups ? e->d_fan : nullptr;
+    SR_TRY(launch_argmax(s, e->d_logits_adm, n_seq, c.t_vocab, e->d_adm + 4 * MAXB, row_map));
     if (e->rows_temp > 0.f) {      // sampling mode: the first token of the new rows is drawn from the admission logits
-        SampleArgs sa{e->d_logits_adm, c.t_vocab, B, 1.0f / e->rows_temp, e->rows_topk, e->rows_topp, 1.0f, nullptr, e->seen_words,
-                      e->rows_seed ^ (0x9E3779B9u * ++e->adm_count), nullptr, e->d_adm_pick, nullptr, 0, 0};
+        SampleArgs sa{e->d_logits_adm, c.t_vocab, n_seq, 1.0f / e->rows_temp, e->rows_topk, e->rows_topp, 1.0f, nullptr, e->seen_words,
+                      e->rows_seed ^ (0x9E3779B9u * ++e->adm_count), nullptr, e->d_adm_pick, nullptr, 0, 0, row_map};
         SR_TRY(launch_sample(s, sa));
     }
-    e->staged_n = B;
+    if (n_groups) {                // the prompts' KV prefixes into the slots of their other forks (d_adm_slots holds every fork's slot in staged order)
+        KvFanoutArgs fa{e->kcache, e->vtcache, (long long)e->kv_layer_elems, c.t_layers, c.t_kv_heads, c.max_ctx, e->d_adm_slots, 0, 0, 0,
+                        e->d_fan + MAXB, n_groups, max_L};
+        SR_TRY(launch_kv_fanout(s, fa));
+    }
+    e->staged_n = n_seq;
     e->staged_off = 0;
-    if (commit) return commit_admission(e, slots, B, s);
+    if (commit) return commit_admission(e, fork_slots ? fork_slots : slots, n_seq, s);
     return 0;
 }
 
@@ -1225,39 +1249,72 @@ int sr_rows_sampling(sr_engine* e, float temperature, int top_k, float top_p, ui
     return 0;
 }
 
-int sr_admit(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* rows, const int32_t* max_new,
-             int n, const void* image_embeds, int n_image_rows, float* logits_out, void* stream) {
-    if (!e || !rows || !max_new) return fail(e, -22, "sr_admit: null argument");
-    if (!e->rows_mode) return fail(e, -22, "sr_admit: call sr_rows_begin first");
+// checks of a fan-out admission (sr_admit_fanout / sr_admit_stage_fanout and their all-ones forms): n prompts, fanout[i] >= 1 sequences each,
+// sum <= MAXB (the staging capacity), every sequence's KV slot (or row) distinct and in range; -> the sum, or a negative error
+static int check_fanout(sr_engine* e, const char* fn, const int32_t* seq_lens, const int32_t* fanout, const int32_t* dst, int n, int dst_hi,
+                        const char* what, const int32_t* max_new) {
+    if (!e->rows_mode) return fail(e, -22, "%s: call sr_rows_begin first", fn);
+    if (e->staged_n) return fail(e, -22, "%s: %d staged sequences are waiting for sr_admit_commit", fn, e->staged_n);
+    if (n < 1 || n > e->c.max_batch) return fail(e, -22, "%s: %d prompts outside 1..%d", fn, n, e->c.max_batch);
+    int total = 0;
     for (int i = 0; i < n; ++i) {
         if (max_new[i] < 1 || max_new[i] > e->c.max_new_tokens || seq_lens[i] + max_new[i] > e->c.max_ctx)
-            return fail(e, -22, "sr_admit: sequence %d (len %d, max_new %d) does not fit max_new_tokens %d / max_ctx %d", i, seq_lens[i],
+            return fail(e, -22, "%s: sequence %d (len %d, max_new %d) does not fit max_new_tokens %d / max_ctx %d", fn, i, seq_lens[i],
                         max_new[i], e->c.max_new_tokens, e->c.max_ctx);
-        if (rows[i] < 0 || rows[i] >= e->c.max_batch) return fail(e, -22, "sr_admit: row %d out of range", rows[i]);
-        for (int j = 0; j < i; ++j)
-            if (rows[i] == rows[j]) return fail(e, -22, "sr_admit: row %d given twice", rows[i]);
+        const int f = fanout ? fanout[i] : 1;
+        if (f < 1) return fail(e, -22, "%s: fanout %d of prompt %d is below 1", fn, f, i);
+        total += f;
+        if (total > MAXB) return fail(e, -22, "%s: %d forked sequences exceed the staging capacity %d (MAXB)", fn, total, MAXB);
     }
-    if (e->staged_n) return fail(e, -22, "sr_admit: %d staged sequences are waiting for sr_admit_commit", e->staged_n);
-    return prefill_impl(e, ids, pos3, seq_lens, rows, n, image_embeds, n_image_rows, logits_out, stream, max_new);      // row r uses KV slot r
+    for (int i = 0; i < total; ++i) {
+        if (dst[i] < 0 || dst[i] >= dst_hi) return fail(e, -22, "%s: %s %d out of range 0..%d", fn, what, dst[i], dst_hi - 1);
+        for (int j = 0; j < i; ++j)
+            if (dst[i] == dst[j]) return fail(e, -22, "%s: %s %d given twice", fn, what, dst[i]);
+    }
+    return total;
+}
+
+// the KV slot each prompt is prefilled into: its first fork's
+static void first_forks(const int32_t* fanout, const int32_t* dst, int n, int32_t* out) {
+    for (int i = 0, k = 0; i < n; k += fanout ? fanout[i] : 1, ++i) out[i] = dst[k];
+}
+
+int sr_admit_fanout(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* fanout, const int32_t* rows,
+                    const int32_t* max_new, int n, const void* image_embeds, int n_image_rows, float* logits_out, void* stream) {
+    enter(e);
+    if (!e || !rows || !max_new || !seq_lens) return fail(e, -22, "sr_admit: null argument");
+    const int total = check_fanout(e, "sr_admit", seq_lens, fanout, rows, n, e->c.max_batch, "row", max_new);
+    if (total < 0) return total;
+    int32_t first[MAXB];
+    first_forks(fanout, rows, n, first);
+    return prefill_impl(e, ids, pos3, seq_lens, first, n, image_embeds, n_image_rows, logits_out, stream, max_new, nullptr, true,     // row r uses KV slot r
+                        fanout, rows);
+}
+
+int sr_admit(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* rows, const int32_t* max_new,
+             int n, const void* image_embeds, int n_image_rows, float* logits_out, void* stream) {
+    return sr_admit_fanout(e, ids, pos3, seq_lens, nullptr, rows, max_new, n, image_embeds, n_image_rows, logits_out, stream);
 }
 
 // Admission in two halves, so that the expensive half can run UNDER the decode steps of the running rows on another (CU-masked)
 // stream: sr_admit_stage = ViT-fed prefill of n sequences into SPARE KV slots + LM head + first-token choice (touches no row state and
 // only admission-owned scratch); sr_admit_commit = install them into free batch rows (row -> KV slot indirection), on the decode
 // stream, between two steps, once the staging stream's work is known to be complete (the caller orders the streams with an event).
+int sr_admit_stage_fanout(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* fanout,
+                          const int32_t* kv_slots, const int32_t* max_new, int n, const void* image_embeds, int n_image_rows, float* logits_out,
+                          void* stream) {
+    enter(e);
+    if (!e || !kv_slots || !max_new || !seq_lens) return fail(e, -22, "sr_admit_stage: null argument");
+    const int total = check_fanout(e, "sr_admit_stage", seq_lens, fanout, kv_slots, n, e->n_slots, "KV slot", max_new);
+    if (total < 0) return total;
+    int32_t first[MAXB];
+    first_forks(fanout, kv_slots, n, first);
+    return prefill_impl(e, ids, pos3, seq_lens, first, n, image_embeds, n_image_rows, logits_out, stream, max_new, nullptr, false, fanout, kv_slots);
+}
+
 int sr_admit_stage(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* kv_slots, const int32_t* max_new,
                    int n, const void* image_embeds, int n_image_rows, float* logits_out, void* stream) {
-    if (!e || !kv_slots || !max_new) return fail(e, -22, "sr_admit_stage: null argument");
-    if (!e->rows_mode) return fail(e, -22, "sr_admit_stage: call sr_rows_begin first");
-    if (e->staged_n) return fail(e, -22, "sr_admit_stage: %d staged sequences are waiting for sr_admit_commit", e->staged_n);
-    for (int i = 0; i < n; ++i) {
-        if (max_new[i] < 1 || max_new[i] > e->c.max_new_tokens || seq_lens[i] + max_new[i] > e->c.max_ctx)
-            return fail(e, -22, "sr_admit_stage: sequence %d (len %d, max_new %d) does not fit max_new_tokens %d / max_ctx %d", i, seq_lens[i],
-                        max_new[i], e->c.max_new_tokens, e->c.max_ctx);
-        for (int j = 0; j < i; ++j)
-            if (kv_slots[i] == kv_slots[j]) return fail(e, -22, "sr_admit_stage: KV slot %d given twice", kv_slots[i]);
-    }
-    return prefill_impl(e, ids, pos3, seq_lens, kv_slots, n, image_embeds, n_image_rows, logits_out, stream, max_new, nullptr, false);
+    return sr_admit_stage_fanout(e, ids, pos3, seq_lens, nullptr, kv_slots, max_new, n, image_embeds, n_image_rows, logits_out, stream);
 }
 
 int sr_admit_commit(sr_engine* e, const int32_t* rows, int n, void* stream) {
@@ -1728,6 +1785,15 @@ int sr_op_sample(const float* logits, int B, int V, float temperature, int top_k
     SampleArgs a{logits, V, B, 1.0f / temperature, top_k, top_p, rep_penalty, seen, (V + 31) / 32, seed, step, reinterpret_cast<long long*>(out),
                  blk_max, n_blk, blk_rows};
     SR_WRAP(launch_sample((hipStream_t)stream, a));
+}
+int sr_op_kv_fanout(void* kcache, void* vtcache, int n_layers, int64_t layer_stride_elems, int n_kv_heads, int max_ctx, int src_slot,
+                    const int32_t* dev_dst_slots, int d, int L, void* stream) {
+    if (!kcache || !vtcache || !dev_dst_slots || src_slot < 0 || d < 1 || L < 1 || L > max_ctx || n_layers < 1 || n_kv_heads < 1 ||
+        layer_stride_elems < (int64_t)(src_slot + 1) * n_kv_heads * max_ctx * 128)
+        return fail(nullptr, -22, "sr_op_kv_fanout: bad arguments (src %d, d %d, L %d, max_ctx %d)", src_slot, d, L, max_ctx);
+    KvFanoutArgs a{static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vtcache), (long long)layer_stride_elems, n_layers, n_kv_heads, max_ctx,
+                   dev_dst_slots, src_slot, L, d, nullptr, 0, 0};
+    SR_WRAP(launch_kv_fanout((hipStream_t)stream, a));
 }
 int sr_op_argmax(const float* logits, int rows, int V, int32_t* out_idx, void* stream) {
     SR_WRAP(launch_argmax((hipStream_t)stream, logits, rows, V, out_idx));

@@ -193,7 +193,7 @@ int launch_gather_rows(hipStream_t s, const bf16_t* in, const int* rows, bf16_t*
 int launch_patchify(hipStream_t s, const uint8_t* img, int h, int w, const bf16_t* lut, bf16_t* out, int ld_out,
                     int patch, int merge, int temporal);
 int launch_f32_to_bf16_pad(hipStream_t s, const float* in, int rows, int cols, bf16_t* out, int ld_out);
-int launch_argmax(hipStream_t s, const float* logits, int rows, int V, int* out_idx);
+int launch_argmax(hipStream_t s, const float* logits, int rows, int V, int* out_idx, const int* row_map = nullptr);   // row i reads logits row row_map[i] (null: i)
 // per-step bookkeeping on the device (one captured graph replays for every step): finishes the greedy argmax from the
 // LM-head partials, logs the token, handles eos / teacher forcing, gathers the next input embedding, advances state
 struct StepArgs {
@@ -221,6 +221,17 @@ struct AdmitArgs {
     const int* kv_slot;         // KV-cache slot of each admitted sequence (null: slot = row)
 };
 int launch_admit_rows(hipStream_t s, const AdmitArgs& a);
+// ------------------------------------------------------------------ kvfork.hip
+// positions [0, L) of KV slot src -> slots dst[0..d), every layer, both caches, one launch (the source is read once)
+struct KvFanoutArgs {
+    bf16_t* kcache; bf16_t* vtcache;        // [layer][slot][kvh][max_ctx][128] and [layer][slot][kvh][128][max_ctx]
+    long long layer_stride;                 // elements from one layer to the next (either cache)
+    int n_layers, n_kvh, max_ctx;
+    const int* dst;                         // destination slots (device)
+    int src, L, d;                          // one fan-out (groups == nullptr) ...
+    const int* groups; int n_groups, max_L;  // ... or n_groups of them: [src | L | first index into dst | d] each (device), max_L >= every L
+};
+int launch_kv_fanout(hipStream_t s, const KvFanoutArgs& a);
 int launch_rows_abort(hipStream_t s, const unsigned row_mask[4], int* finished);      // finished[b] = 1 for every bit b of the 128-bit row mask
 // ------------------------------------------------------------------ sample.hip
 struct SampleArgs {
@@ -230,6 +241,7 @@ struct SampleArgs {
     unsigned seed; const int* step;         // RNG stream: (seed, row, step[row])
     long long* out;                         // [B] chosen token
     const float* blk_max; int n_blk, blk_rows;   // optional: the LM head's per-block maxima [B][n_blk], block j = ids [j*blk_rows, (j+1)*blk_rows)
+    const int* row_map = nullptr;           // optional: draw b reads logits (and blk_max) row row_map[b]; its RNG stream stays (seed, b, step[b])
 };
 int launch_sample(hipStream_t s, const SampleArgs& a);
 int launch_scatter_rows(hipStream_t s, const int* rows, const long long* src, long long* dst, int n);   // dst[rows[i]] = src[i]

@@ -69,7 +69,8 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     __shared__ int s_cnt;
     __shared__ float s_red[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* row = a.logits + (size_t)b * a.V;
+    const int lr = a.row_map ? a.row_map[b] : b;         // logits row (forks of one prompt share it); b keeps the RNG stream
+    const float* row = a.logits + (size_t)lr * a.V;
     const unsigned* seen = a.seen ? a.seen + (size_t)b * a.seen_words : nullptr;
     const int K = a.top_k;
     // ---- candidate reduction through the LM head's per-block maxima (exact): an element of the global top-K is >= the K-th
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     const int R = a.blk_rows;
     bool filtered = false;
     if (a.blk_max && !seen && a.n_blk > K && R > 0) {
-        const float* bm = a.blk_max + (size_t)b * a.n_blk;
+        const float* bm = a.blk_max + (size_t)lr * a.n_blk;
         uint32_t pfx = 0;
         int need_b = K;
 #pragma unroll
@@ -289,7 +290,8 @@ __global__ __launch_bounds__(NT) void k_sample_full(SampleArgs a) {
     __shared__ int s_i[4];
     __shared__ float s_scan[NT];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* row = a.logits + (size_t)b * a.V;
+    const int lr = a.row_map ? a.row_map[b] : b;         // logits row (forks of one prompt share it); b keeps the RNG stream
+    const float* row = a.logits + (size_t)lr * a.V;
     const unsigned* seen = a.seen ? a.seen + (size_t)b * a.seen_words : nullptr;
     auto adj = [&](int id) -> float {
         float l = row[id];
@@ -435,14 +437,15 @@ __global__ void k_mark_chosen(const long long* chosen, unsigned* seen, int seen_
 }
 
 __global__ void k_scatter_rows(const int* rows, const long long* src, long long* dst, int n) {
-    const int i = threadIdx.x;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[rows[i]] = src[i];
 }
 
 }  // namespace
 
 int launch_scatter_rows(hipStream_t s, const int* rows, const long long* src, long long* dst, int n) {
-    hipLaunchKernelGGL(k_scatter_rows, dim3(1), dim3(64), 0, s, rows, src, dst, n);
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(k_scatter_rows, dim3((n + 63) / 64), dim3(64), 0, s, rows, src, dst, n);     // (one block of 64 left rows 64.. of a larger commit unset)
     SR_CHECK_LAUNCH();
     return 0;
 }

@@ -19,6 +19,9 @@ the same policy is run over the process group's key-value store (c10d TCPStore -
 
 With the reference's cap of 128 a batch of <= 128 x world requests is dealt out at once, interleaved over the ranks; a cap at the
 engines' row count makes it work-conserving for skewed answer lengths (tests/test_host_cpu.py shows both).
+
+A request with num_return_sequences n > 1 occupies n of its worker's running sequences (the engine fans it out into n rows): the cap
+counts sequences, and what travels back to the owner is whatever the request loop reported -- its n token lists.
 """
 from __future__ import annotations
 
@@ -62,10 +65,11 @@ class CrossRankDispatcher:
     calls ``run`` with its own requests; ``run`` returns {local index: token ids}."""
 
     def __init__(self, store, rank: int, world: int, round_id: int, max_running_requests: int = 128, poll_s: float = 0.002,
-                 timeout_s: float = 3600.0):
+                 timeout_s: float = 3600.0, num_return_sequences: int = 1):
         from torch.distributed import PrefixStore
         self.store = PrefixStore(f"sr_dispatch/{int(round_id)}/", store)
         self.rank, self.world, self.cap, self.poll_s, self.timeout_s = int(rank), int(world), int(max_running_requests), poll_s, timeout_s
+        self.n = max(1, int(num_return_sequences))          # sequences per request (every request of a round shares the generation config)
         self.errors: List[BaseException] = []
         self.stats = {"sent_to": [0] * self.world, "served_here": 0, "served_for_others": 0, "shipped_out": 0}
 
@@ -121,7 +125,7 @@ class CrossRankDispatcher:
                 while True:
                     load = [sent[r] - self._counter(f"done/{r}") for r in range(self.world)]
                     r = min(range(self.world), key=lambda k: (load[k], k))
-                    if load[r] < self.cap:
+                    if (load[r] + 1) * self.n <= self.cap or load[r] == 0:      # n sequences per request; an idle worker always takes one
                         break
                     if self.aborted():                    # another rank failed: stop dealing at once instead of spinning into the timeout
                         raise RuntimeError("dispatcher: another rank aborted the round")
@@ -144,7 +148,8 @@ class CrossRankDispatcher:
         """requests: this rank's single-request DataProtos in local order.  add_request(req): hand a request (meta_info[request_id_key]
         already set to the global id) to the local engine's request loop.  make_result_sink(cb): install cb(gid, token_ids) as the
         completion callback of that loop.  make_request(batch, non_tensor_batch, meta_info): rebuild a request that arrived from
-        another rank.  Returns {local index: token ids} for all of this rank's own requests."""
+        another rank.  Returns {local index: what the request loop reported} (token ids; n token lists with num_return_sequences n) for all of
+        this rank's own requests."""
         n_local = len(requests)
         self._set(f"n/{self.rank}", n_local)
         sizes = [self._get_int(f"n/{r}") for r in range(self.world)]

@@ -251,8 +251,10 @@ class Engine:
         L.check(self.lib.sr_rows_sampling(self._h, C.c_float(temperature), int(top_k), C.c_float(top_p), int(seed) & 0xffffffff), self._h, "sr_rows_sampling")
 
     def admit(self, rows: Sequence[int], ids: Sequence[np.ndarray], pos3: Sequence[np.ndarray], max_new: Sequence[int],
-              image_embeds: torch.Tensor | None = None, return_logits: bool = False):
-        """Prefill sequences into free batch rows without disturbing running ones; row i stops after max_new[i] tokens."""
+              image_embeds: torch.Tensor | None = None, return_logits: bool = False, fanout: Sequence[int] | None = None):
+        """Prefill sequences into free batch rows without disturbing running ones; row i stops after max_new[i] tokens.
+        fanout: prompt i becomes fanout[i] sequences (prefilled once, its KV prefix copied on the device); `rows` then holds one row per
+        sequence, prompt-major, and max_new stays per prompt.  The logits (return_logits) have one row per prompt."""
         n = len(ids)
         lens = np.array([len(x) for x in ids], dtype=np.int32)
         flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
@@ -264,16 +266,24 @@ class Engine:
         if image_embeds is not None:
             image_embeds = image_embeds.contiguous()
             assert image_embeds.dtype == torch.bfloat16
-        L.check(self.lib.sr_admit(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
-                                  rw.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n,
-                                  C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None, n_img,
-                                  C.c_void_p(logits.data_ptr()) if logits is not None else None, self._s()), self._h, "sr_admit")
+        emb_p = C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None
+        lg_p = C.c_void_p(logits.data_ptr()) if logits is not None else None
+        if fanout is None:
+            L.check(self.lib.sr_admit(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
+                                      rw.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n, emb_p, n_img, lg_p, self._s()), self._h, "sr_admit")
+        else:
+            fo = np.asarray(list(fanout), dtype=np.int32)
+            assert len(fo) == n and len(rw) == int(fo.sum()), "fanout: one entry per prompt, one row per forked sequence"
+            L.check(self.lib.sr_admit_fanout(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
+                                             fo.ctypes.data_as(L._i32p), rw.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n, emb_p, n_img,
+                                             lg_p, self._s()), self._h, "sr_admit_fanout")
         return logits
 
     def admit_stage(self, kv_slots: Sequence[int], ids: Sequence[np.ndarray], pos3: Sequence[np.ndarray], max_new: Sequence[int],
-                    image_embeds: torch.Tensor | None = None):
+                    image_embeds: torch.Tensor | None = None, fanout: Sequence[int] | None = None, return_logits: bool = False):
         """First half of an admission, on the CURRENT torch stream (normally a CU-masked side stream): prefill into spare KV slots, LM
-        head, first token.  No row state is touched; admit_commit installs the sequences into rows later."""
+        head, first token.  No row state is touched; admit_commit installs the sequences into rows later.  fanout: as admit (kv_slots then
+        has one slot per forked sequence, prompt-major)."""
         n = len(ids)
         lens = np.array([len(x) for x in ids], dtype=np.int32)
         flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
@@ -284,10 +294,20 @@ class Engine:
         if image_embeds is not None:
             image_embeds = image_embeds.contiguous()
             assert image_embeds.dtype == torch.bfloat16
-        L.check(self.lib.sr_admit_stage(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
-                                        sl.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n,
-                                        C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None, n_img, None, self._s()),
-                self._h, "sr_admit_stage")
+        emb_p = C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None
+        logits = torch.empty(n, self.geom.text.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
+        lg_p = C.c_void_p(logits.data_ptr()) if logits is not None else None
+        if fanout is None:
+            L.check(self.lib.sr_admit_stage(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
+                                            sl.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n, emb_p, n_img, lg_p, self._s()),
+                    self._h, "sr_admit_stage")
+        else:
+            fo = np.asarray(list(fanout), dtype=np.int32)
+            assert len(fo) == n and len(sl) == int(fo.sum()), "fanout: one entry per prompt, one KV slot per forked sequence"
+            L.check(self.lib.sr_admit_stage_fanout(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
+                                                   fo.ctypes.data_as(L._i32p), sl.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n, emb_p,
+                                                   n_img, lg_p, self._s()), self._h, "sr_admit_stage_fanout")
+        return logits
 
     def admit_commit(self, rows: Sequence[int]):
         """Second half, on the decode stream between two steps: batch row rows[i] takes over the i-th staged sequence (and its KV slot)."""

@@ -5,6 +5,11 @@ A request is admitted into a free row as soon as one exists (its prompt is prefi
 all rows decode together -- one hipGraph replay per token for the whole batch -- and a row is released the moment its
 sequence hits an eos token or its own max_new_tokens.  Greedy decoding; a request's tokens do not depend on what shares
 the batch with it (per-row arithmetic is independent of the other rows).
+
+A request with n > 1 (the reference's num_return_sequences) is admitted ONCE and fanned out into n rows: its prompt is prefilled into
+the KV slot of its first fork, the engine copies that prefix into the other forks' slots on the device (k_kv_fanout) and every fork
+draws its own first token.  It takes n rows and n KV slots, and is reported once, when its last fork finishes, with its n token lists
+in fork order.
 """
 from __future__ import annotations
 
@@ -39,6 +44,7 @@ class Request:
     grids: list = field(default_factory=list)      # (t, h, w) per image
     tag: object = None
     aborted: bool = False                 # set by the serving loop: the row runs to its end, its result is discarded
+    n: int = 1                            # sequences sampled from this prompt (forks of one admission); n > 1: reported with n token lists
 
 
 class ContinuousBatcher:
@@ -56,8 +62,10 @@ class ContinuousBatcher:
         self.engine, self.eos, self.pad_id, self.steps_per_poll = engine, [int(e) for e in eos], int(pad_id), steps_per_poll
         self._ev = [] if time_phases else None
         self.overlap = bool(overlap) and engine.kv_slots > engine.cfg.max_batch
-        self.staged = None                     # (requests, kv slots, completion event) of the admission in flight
+        self.staged = None                     # (request of each sequence, kv slots, completion event, image features, fork of each sequence) of the admission in flight
         self.row_slot: Dict[int, int] = {}
+        self.row_fork: Dict[int, int] = {}       # row -> which of its request's n forks it decodes
+        self._parts: Dict[int, list] = {}         # id(request) -> [request, token lists by fork, forks still running] of an n > 1 request
         self.free_slots = deque(range(engine.kv_slots))
         self._dec_last = None
         self._commit_ev = None
@@ -95,7 +103,7 @@ class ContinuousBatcher:
         self.pending: deque = deque()
         # rounds / host_ms / poll_wait_ms (round 5): scheduling rounds, host time spent in them OUTSIDE the poll's wait for the device, and that wait --
         # with N ranks on one node a flat 1 -> N curve shows here as host_ms per round growing with N (host contention) rather than poll_wait_ms
-        self.stats = {"admitted": 0, "steps": 0, "admissions": 0, "staged_shared": 0, "steps_shared": 0, "shares": [], "rounds": 0, "host_ms": 0.0, "poll_wait_ms": 0.0}
+        self.stats = {"admitted": 0, "admitted_prompts": 0, "steps": 0, "admissions": 0, "staged_shared": 0, "steps_shared": 0, "shares": [], "rounds": 0, "host_ms": 0.0, "poll_wait_ms": 0.0}
         engine.rows_begin()
         if sampling:
             engine.rows_sampling(float(sampling["temperature"]), int(sampling["top_k"]), float(sampling.get("top_p", 1.0)), int(sampling.get("seed", 0)))
@@ -130,6 +138,8 @@ class ContinuousBatcher:
         if len(req.ids) > cfg.max_prefill_tokens or npatch > cfg.max_patches or len(req.ids) + 1 > cfg.max_ctx:
             raise ValueError(f"request of {len(req.ids)} tokens / {npatch} patches exceeds the engine's capacity "
                              f"(max_prefill_tokens {cfg.max_prefill_tokens}, max_patches {cfg.max_patches}, max_ctx {cfg.max_ctx})")
+        if not 1 <= int(req.n) <= cfg.max_batch:          # its forks decode side by side: all n of them need a row
+            raise ValueError(f"request of n = {req.n} sequences exceeds the engine's capacity (1 <= n <= max_batch {cfg.max_batch})")
         self.pending.append(req)
 
     def idle(self) -> bool:
@@ -142,7 +152,8 @@ class ContinuousBatcher:
         n0 = len(self.pending)
         self.pending = deque(r for r in self.pending if not match(r))
         hit = n0 - len(self.pending)
-        rows = [row for row, r in self.active.items() if match(r) and not r.aborted]
+        rows = [row for row, r in self.active.items() if match(r) and not r.aborted]      # (every running fork of a fan-out request)
+        hit += len({id(self.active[row]) for row in rows}) - len(rows)
         for row in rows:
             self.active[row].aborted = True
         if rows:
@@ -156,19 +167,11 @@ class ContinuousBatcher:
         return hit + len(rows)
 
     def _admit(self):
-        cfg = self.engine.cfg
-        grp, ntok, npatch = [], 0, 0
-        while self.pending and len(grp) < len(self.free):
-            r = self.pending[0]
-            np_r = sum(t * h * w for t, h, w in r.grids)
-            if grp and (ntok + len(r.ids) > cfg.max_prefill_tokens or npatch + np_r > cfg.max_patches):
-                break
-            grp.append(self.pending.popleft())
-            ntok += len(r.ids)
-            npatch += np_r
+        grp = self._take_group(len(self.free))
         if not grp:
             return
-        rows = [self.free.popleft() for _ in grp]
+        n_seq = sum(r.n for r in grp)
+        rows = [self.free.popleft() for _ in range(n_seq)]
         emb = None
         ims = [im for r in grp for im in r.images]
         t0 = self._mark()
@@ -177,22 +180,49 @@ class ContinuousBatcher:
                 pix = torch.cat([self.engine.patchify(im) for im in ims], dim=0)
                 emb = self.engine.vit_forward(pix, [g for r in grp for g in r.grids])
             t1 = self._mark()
-            self.engine.admit(rows, [r.ids for r in grp], [r.pos3 for r in grp], [r.max_new for r in grp], emb)
+            self.engine.admit(rows, [r.ids for r in grp], [r.pos3 for r in grp], [r.max_new for r in grp], emb, fanout=self._fanout(grp))
         except BaseException:
             self.free.extendleft(reversed(rows))
             raise
         self._span("vit", t0, t1)
         self._span("prefill", t1, self._mark())
-        for row, r in zip(rows, grp):
+        for row, (r, j) in zip(rows, self._forks(grp)):
             self.active[row] = r
-        self.stats["admitted"] += len(grp)
+            self.row_fork[row] = j
+        self.stats["admitted"] += n_seq
+        self.stats["admitted_prompts"] += len(grp)
         self.stats["admissions"] += 1
+
+    @staticmethod
+    def _fanout(grp):
+        """the engine's fanout argument of a group: None (every request one sequence: the plain admission) or the n of each request"""
+        return [r.n for r in grp] if any(r.n > 1 for r in grp) else None
+
+    @staticmethod
+    def _forks(grp):
+        """(request, fork index) of every sequence of a group, prompt-major: the engine's staging order"""
+        return [(r, j) for r in grp for j in range(r.n)]
+
+    def _report(self, req, fork, toks, on_complete):
+        """an n = 1 request is reported as it always was; an n > 1 request once its last fork is done, with the n lists in fork order (an
+        aborted one not at all)"""
+        if req.n == 1:
+            on_complete(req, toks)
+            return
+        part = self._parts.setdefault(id(req), [req, [None] * req.n, req.n])
+        part[1][fork] = toks
+        part[2] -= 1
+        if part[2] == 0:
+            del self._parts[id(req)]
+            if not req.aborted:
+                on_complete(req, part[1])
 
     # ------------------------------------------------------------------ overlapped admission (stage on a side stream, commit into rows)
     def _take_group(self, limit: int):
+        """requests from the head of the queue whose sequences (n each) fit `limit` rows / slots and whose prompts fit one admission"""
         cfg = self.engine.cfg
-        grp, ntok, npatch = [], 0, 0
-        while self.pending and len(grp) < limit:
+        grp, ntok, npatch, nseq = [], 0, 0, 0
+        while self.pending and nseq + self.pending[0].n <= limit:
             r = self.pending[0]
             np_r = sum(t * h * w for t, h, w in r.grids)
             if grp and (ntok + len(r.ids) > cfg.max_prefill_tokens or npatch + np_r > cfg.max_patches):
@@ -200,6 +230,7 @@ class ContinuousBatcher:
             grp.append(self.pending.popleft())
             ntok += len(r.ids)
             npatch += np_r
+            nseq += r.n
         return grp
 
     def _set_cus(self, n):
@@ -297,7 +328,8 @@ class ContinuousBatcher:
         grp = self._take_group(min(len(self.free_slots), self.engine.cfg.max_batch))
         if not grp:
             return
-        slots = [self.free_slots.popleft() for _ in grp]
+        slots = [self.free_slots.popleft() for _ in range(sum(r.n for r in grp))]
+        # (a prompt counts once: its forks share its ViT and prefill; the prefix copy is a few hundred microseconds at most)
         units = sum(self._wp * sum(t * h * w for t, h, w in r.grids) + self._wt * len(r.ids) for r in grp)
         # with rows running: the admission's half of the chip; with nothing to decode there is nothing to share the chip with
         shared = "_shared" if self.active else ""
@@ -311,7 +343,7 @@ class ContinuousBatcher:
             self.stats["shares"].append(self._share)
             s = self.streams.admit
             s.wait_stream(torch.cuda.current_stream(self.engine.device))     # the request's images were produced on the caller's stream
-            self.stats["staged_shared"] += len(grp)
+            self.stats["staged_shared"] += len(slots)
             if self._commit_ev is not None:
                 s.wait_event(self._commit_ev)          # the previous group's last commit reads the engine's admission scratch
         else:
@@ -339,19 +371,21 @@ class ContinuousBatcher:
                 pix = torch.cat([self.engine.patchify(im) for im in ims], dim=0)
                 emb = self.engine.vit_forward(pix, [g for r in grp for g in r.grids])
             t1 = self._mark()
-            self.engine.admit_stage(slots, [r.ids for r in grp], [r.pos3 for r in grp], [r.max_new for r in grp], emb)
+            self.engine.admit_stage(slots, [r.ids for r in grp], [r.pos3 for r in grp], [r.max_new for r in grp], emb, fanout=self._fanout(grp))
             self._span("vit" + shared, t0, t1)
             self._span("prefill" + shared, t1, self._mark())
             ev = torch.cuda.Event(enable_timing=cal)
             ev.record(s)
             if cal:
                 self._cal_adm = (c0, ev, units)
-        self.staged = (grp, slots, ev, emb)            # emb kept alive until the side stream is done with it
+        forks = self._forks(grp)
+        self.staged = ([r for r, _ in forks], slots, ev, emb, [j for _, j in forks])      # one entry per sequence; emb kept alive until the side stream is done with it
         self.stats["admissions"] += 1
+        self.stats["admitted_prompts"] += len(grp)
 
     def _commit(self):
         """install as many staged sequences as there are free rows (in staging order); the rest waits for the next rows"""
-        grp, slots, ev, _ = self.staged
+        grp, slots, ev, _, forks = self.staged
         k = min(len(self.free), len(grp))
         rows = [self.free.popleft() for _ in range(k)]
         s = self._use_decode_stream(self.streams.decode_full)
@@ -360,16 +394,17 @@ class ContinuousBatcher:
             self.engine.admit_commit(rows)
             self._commit_ev = torch.cuda.Event()
             self._commit_ev.record(s)
-        for row, slot, r in zip(rows, slots[:k], grp[:k]):
+        for row, slot, r, j in zip(rows, slots[:k], grp[:k], forks[:k]):
             self.active[row] = r
             self.row_slot[row] = slot
+            self.row_fork[row] = j
             self._cnt_last[row] = 0
         dead = [row for row, r in zip(rows, grp[:k]) if r.aborted]      # aborted while they waited for a row: stop before the first step
         if dead:
             with torch.cuda.stream(s):
                 self.engine.rows_abort(dead)
         self.stats["admitted"] += k
-        del grp[:k], slots[:k]
+        del grp[:k], slots[:k], forks[:k]
         if not grp:
             self.staged = None
 
@@ -378,7 +413,8 @@ class ContinuousBatcher:
             self._commit()                             # (ordered after the staging stream through the event, not on the host)
         if not self.active and self.staged is None and self.pending:
             self._stage()                              # nothing to decode meanwhile: whole chip, install at once
-            self._commit()
+            if self.staged is not None:
+                self._commit()
         if not self.active:
             if self.staged is not None:
                 self.staged[2].synchronize()
@@ -457,7 +493,7 @@ class ContinuousBatcher:
                 buf = self.engine.rows_tokens(rows, counts)
                 ev = torch.cuda.Event()
                 ev.record(s)
-                self._deferred.append(([self.active.pop(r) for r in rows], counts, buf, ev))
+                self._deferred.append(([(self.active.pop(r), self.row_fork.pop(r, 0)) for r in rows], counts, buf, ev))
                 for row in rows:
                     self.free.append(row)
                     self.free_slots.append(self.row_slot.pop(row))
@@ -481,8 +517,8 @@ class ContinuousBatcher:
             # raster tail and result exchange) is ordered behind the decode steps and never lands on the null stream, which would synchronise with the
             # CU-masked (blocking) streams -- i.e. wait for a staged admission and hold every later decode chunk behind itself
             with (torch.cuda.stream(self._dec_last) if (self.overlap and self._dec_last is not None) else contextlib.nullcontext()):
-                for req, n, toks in zip(reqs, counts, host):
-                    on_complete(req, toks[:n].tolist())
+                for (req, fork), n, toks in zip(reqs, counts, host):
+                    self._report(req, fork, toks[:n].tolist(), on_complete)
 
     def _poll(self):
         import time
@@ -519,7 +555,7 @@ class ContinuousBatcher:
             req = self.active.pop(row)
             toks = self.engine.row_tokens(row, int(cnt[row])).cpu().tolist()
             self.free.append(row)
-            on_complete(req, toks)
+            self._report(req, self.row_fork.pop(row, 0), toks, on_complete)
 
     def _hand_back(self):
         """back to the caller's stream, the engine's CU hint back to the whole chip"""
@@ -537,7 +573,7 @@ class ContinuousBatcher:
         self._hand_back()
 
     def run(self, requests: Sequence[Request]) -> List[List[int]]:
-        """Serve a fixed list of requests; returns their token lists in request order."""
+        """Serve a fixed list of requests; returns their token lists in request order (an n > 1 request: its n lists)."""
         order = {id(r): i for i, r in enumerate(requests)}
         out: List[Optional[List[int]]] = [None] * len(requests)
         for r in requests:
