@@ -152,6 +152,21 @@ int sr_decode_sample(sr_engine* e, int B, int max_new, const int32_t* host_eos, 
                      int top_k, float top_p, float repetition_penalty, uint32_t seed, int32_t* dev_tokens_out, int use_graph,
                      void* stream, int* steps_done);
 
+/* Beam search (the reference's num_beams > 1: HF GenerationMixin._beam_search with do_sample=False, early_stopping=False) over the G
+ * prompts of the last sr_prefill, W beams each: every prompt is fanned out to W KV slots on the device, and every step (one captured graph
+ * with use_graph) feeds each beam its token, runs the forward, takes the top K = max(2, 1 + n_eos) * W candidates running + log_softmax
+ * of each group (ties: lower beam * V + token), picks the next W running beams, merges the candidates among the first W that end (an eos
+ * token, or the max_new-th token) into the group's finished list with score cum / gen_len^length_penalty, applies HF's early-stop
+ * heuristic, and reorders the KV slots (the first child of a parent inherits its slot, the others take the slots of childless parents and
+ * get a copy of the parent's generated suffix).  Outputs (host): tokens_out [G][R][max_new] (eos included, then pad_id), scores_out
+ * [G][R], lengths_out [G][R] -- the R best finished hypotheses of every group, best first.  Optional (device): dev_logits_trace
+ * [max_new][G*W][V] float32 (eager launches), dev_beam_trace [max_new][G*W][2] int32 (parent beam, token; -1 -1 for steps not run,
+ * -1 pad_id for a group that has stopped).  Refused, with the value named: G*W > max_batch, W > 8, K > 64, R > W, context overflow,
+ * continuous-batching mode.  A new sr_prefill is required afterwards. */
+int sr_decode_beam(sr_engine* e, int G, int W, int R, int max_new, const int32_t* host_eos, int n_eos, int32_t pad_id, float length_penalty,
+                   int32_t* tokens_out, float* scores_out, int32_t* lengths_out, float* dev_logits_trace, int32_t* dev_beam_trace, int use_graph,
+                   void* stream, int* steps_done);
+
 /* One decode step with the token choice left to the caller -- the `sr_decode_step` of SURVEY section 8(B); this is what a
  * sampling caller (temperature / top-k / top-p of vllm_strategy.py:289-309) or the logits-gathering verification
  * mode of the multi-GPU path drives.  Feeds dev_last_ids[b] (int64, device; NULL = the greedy token of the logits the
@@ -330,6 +345,18 @@ int sr_op_argmax(const float* logits, int rows, int V, int32_t* out_idx, void* s
  * slots dev_dst_slots[0..d) (int32, device), all layers, one launch; nothing else is written.  max_ctx % 64 == 0. */
 int sr_op_kv_fanout(void* kcache, void* vtcache, int n_layers, int64_t layer_stride_elems, int n_kv_heads, int max_ctx, int src_slot,
                     const int32_t* dev_dst_slots, int d, int L, void* stream);
+/* the KV suffix copy of sr_decode_beam on caller-provided caches (layout as sr_op_kv_fanout): for each of the n entries (src slot, dst slot,
+ * L0, L1) of dev_copies (int32 [n][4], device; src < 0: skipped), positions [L0, L1) of src -> dst, all layers, one launch; nothing else
+ * is written.  max_len >= every L1 - L0 sizes the grid. */
+int sr_op_kv_suffix_copy(void* kcache, void* vtcache, int n_layers, int64_t layer_stride_elems, int n_kv_heads, int max_ctx,
+                         const int32_t* dev_copies, int n, int max_len, void* stream);
+/* one beam-search step (row statistics + group select of sr_decode_beam, no KV reorder) on caller-provided float32 logits [G*W, V] and
+ * device state: dev_scores float32 [G*W] running scores (in / out), dev_fin [G*W] finished entries (float score, int32 step, parent beam,
+ * token: 16 bytes each, best first) with counts dev_fin_n int32 [G] (in / out), dev_done int32 [G] stop flags (in / out), dev_trace int32
+ * [max_new][G*W][2] (row `step` written: parent beam, token), dev_next_tok int64 [G*W].  Synchronous. */
+int sr_op_beam_select(const float* dev_logits, int G, int W, int V, const int32_t* host_eos, int n_eos, int step, int max_new,
+                      float length_penalty, int32_t pad_id, float* dev_scores, void* dev_fin, int32_t* dev_fin_n, int32_t* dev_done,
+                      int32_t* dev_trace, int64_t* dev_next_tok, void* stream);
 /* the sampling kernel on caller-provided float32 logits [B, V]; dev_seen: optional bitmask [B][(V+31)/32]; dev_step: optional
  * int32 [B]; dev_blk_max: optional per-block maxima [B][n_blk] of blk_rows consecutive ids each (the LM head's argmax partials):
  * the exact top-k is then searched only in the blocks that can contain it */

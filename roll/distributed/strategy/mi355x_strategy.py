@@ -304,8 +304,9 @@ class Mi355xStrategy(InferenceStrategy):
     def generate(self, batch: DataProto, generation_config) -> torch.Tensor:
         self._finish_weight_update()
         gc = dict(generation_config)
-        if gc.get("num_beams", 1) > 1:
-            raise NotImplementedError("beam search is not part of the inference hot path")
+        W = int(gc.get("num_beams", 1) or 1)
+        if W > 1:
+            check_beam_config(gc, self.engine.cfg.max_batch)
         greedy = sampling.is_greedy(gc) and float(gc.get("repetition_penalty", 1.0) or 1.0) == 1.0
         n = int(gc.get("num_return_sequences", 1) or 1)
         input_ids = batch.batch["input_ids"]
@@ -331,7 +332,10 @@ class Mi355xStrategy(InferenceStrategy):
         tk = -1 if tk is None else int(tk)
         on_device = not greedy and tk <= 1024 and float(gc.get("temperature", 1.0)) > 1e-5
         rp1 = float(gc.get("repetition_penalty", 1.0) or 1.0) == 1.0
-        if greedy or (on_device and rp1):
+        if W > 1:
+            self._generate_beam(prepared, results, gc, W, n, eos, pad, max_new)
+            i = B
+        elif greedy or (on_device and rp1):
             # the stages are decoupled: the scheduler admits the prompts in capacity-sized groups (ViT + prefill into free KV rows)
             # and ALL filled rows decode together -- a batch larger than one admission, or than max_batch, still decodes at full
             # width, and rows freed by short answers are refilled at once (socioreasoner_amd/serving.py).  Sampled n > 1: one request of n
@@ -405,6 +409,38 @@ class Mi355xStrategy(InferenceStrategy):
         results = [r for rs in results for r in rs]
         output_ids = hostops.gather_outputs_to_pad_tensor(results, pad, device=input_ids.device)
         return hostops.concatenate_input_and_output(input_ids, output_ids, n)
+
+    def _generate_beam(self, prepared, results, gc: dict, W: int, R: int, eos, pad: int, max_new: int):
+        """num_beams W > 1 (HF _beam_search, do_sample=False): the prompts in chunks of max_batch // W (prompt tokens and image patches
+        permitting), ViT and prefill once per chunk, then beam search on the device; results[k] gets prompt k's R hypotheses, best first,
+        each cut after its eos."""
+        lp = float(gc.get("length_penalty", 1.0) if gc.get("length_penalty") is not None else 1.0)
+        per = max(1, self.engine.cfg.max_batch // W)
+        B, i = len(prepared), 0
+        while i < B:
+            grp, ntok, npatch = [], 0, 0
+            while i < B and len(grp) < per:
+                ids_i, _, _, grids = prepared[i]
+                np_i = sum(t * h * w for t, h, w in grids)
+                if grp and (ntok + len(ids_i) > self.engine.cfg.max_prefill_tokens or npatch + np_i > self.engine.cfg.max_patches):
+                    break
+                grp.append(i)
+                ntok += len(ids_i)
+                npatch += np_i
+                i += 1
+            ims = [im for k in grp for im in prepared[k][2]]
+            grids = [g_ for k in grp for g_ in prepared[k][3]]
+            emb = None
+            if ims:
+                pix = torch.cat([self.engine.patchify(im) for im in ims], dim=0)
+                emb = self.engine.vit_forward(pix, grids)
+            room = self.engine.cfg.max_ctx - max(len(prepared[k][0]) for k in grp)
+            if room < 1:
+                raise ValueError(f"prompt of {self.engine.cfg.max_ctx - room} tokens leaves no room in max_ctx {self.engine.cfg.max_ctx}")
+            self.engine.prefill([prepared[k][0] for k in grp], [prepared[k][1] for k in grp], emb)
+            toks, _, lens = self.engine.decode_beam(W, min(max_new, room), R, lp, eos=eos, pad_id=pad)
+            for g_, k in enumerate(grp):
+                results[k] = [toks[g_, r, :int(lens[g_, r])].tolist() for r in range(R)]
 
     def _sample_loop(self, logits: torch.Tensor, prompt_ids, max_new: int, eos, pad: int, gc: dict) -> torch.Tensor:
         """Token-by-token decode with the draw on the host side of the C ABI (sr_decode_step).  -> int64 [B, max_new]"""
@@ -485,7 +521,8 @@ class Mi355xStrategy(InferenceStrategy):
                     dev_sampling = not greedy and tk <= 1024 and float(gc.get("temperature", 1.0)) > 1e-5
                     n_req = int(gc.get("num_return_sequences", 1) or 1)
                     rows_ok = (hasattr(self.engine, "rows_begin") and rp1 and (greedy or dev_sampling)
-                               and n_req <= getattr(getattr(self.engine, "cfg", None), "max_batch", 1))
+                               and n_req <= getattr(getattr(self.engine, "cfg", None), "max_batch", 1)
+                               and int(gc.get("num_beams", 1) or 1) == 1)          # beam search: the static path (generate's beam branch)
                     if not rows_ok:
                         sampled.append(req)
                     else:
@@ -548,6 +585,10 @@ class Mi355xStrategy(InferenceStrategy):
             if sampled and (len(sampled) >= self.max_batch or self.command_queue.empty()):
                 todo, sampled = sampled[: self.max_batch], sampled[self.max_batch:]
                 gc = todo[0].meta_info.get("generation_config")
+                if int((gc or {}).get("num_beams", 1) or 1) > 1:     # beam requests are served only with their own generation config
+                    same = [r for r in todo if r.meta_info.get("generation_config") == gc]
+                    sampled = [r for r in todo if r.meta_info.get("generation_config") != gc] + sampled
+                    todo = same
                 if batcher is not None and not batcher.idle():
                     sampled = todo + sampled      # rows are running: the static path needs the whole engine, wait
                 else:
@@ -568,6 +609,21 @@ class Mi355xStrategy(InferenceStrategy):
                                            **{k: (round(v, 1) if isinstance(v, float) else v) for k, v in batcher.stats.items()
                                               if k in ("steps", "steps_shared", "admissions", "rounds", "host_ms", "poll_wait_ms", "shares", "share_model")}})
                 return
+
+
+def check_beam_config(gc: dict, max_batch: int):
+    """The beam-search settings generate() serves (HF _beam_search with do_sample=False, early_stopping=False); the rest is refused by name."""
+    W = int(gc.get("num_beams", 1) or 1)
+    R = int(gc.get("num_return_sequences", 1) or 1)
+    if not 1 <= R <= W:
+        raise ValueError(f"num_return_sequences={R} must be between 1 and num_beams={W}")
+    if W > min(8, max_batch):
+        raise ValueError(f"num_beams={W} exceeds the engine's limit of {min(8, max_batch)} beams per prompt")
+    if float(gc.get("repetition_penalty", 1.0) or 1.0) != 1.0:
+        raise NotImplementedError(f"repetition_penalty={gc.get('repetition_penalty')} together with num_beams={W} is not supported")
+    es = gc.get("early_stopping", False)
+    if es is True or es == "never":
+        raise NotImplementedError(f"early_stopping={es!r} together with num_beams={W} is not supported (only early_stopping=False)")
 
 
 class SegRasterStrategy(InferenceStrategy):

@@ -172,6 +172,13 @@ struct sr_engine {
     hipGraphExec_t sgraph = nullptr;      // sampled decode step: bookkeeping + forward + k_sample
     int sg_B = -1, sg_neos = -1, sg_pad = 0, sg_topk = 0, sg_px = 0; float sg_it = 0.f, sg_topp = 0.f, sg_rp = 0.f; unsigned sg_seed = 0;
     int prefilled_B = 0;
+    int pre_len[MAXB], pre_slot[MAXB], pre_pos[MAXB];   // static prefill: every sequence's length, KV slot and last position (sr_decode_beam)
+    // beam search (sr_decode_beam): device state allocated on first use, freed on destroy
+    void* beam_mem = nullptr;
+    BeamPart* bm_part = nullptr; float* bm_scores = nullptr; long long* bm_tok = nullptr; BeamTrace* bm_trace = nullptr; BeamFin* bm_fin = nullptr;
+    int *bm_fin_n = nullptr, *bm_done = nullptr, *bm_stop = nullptr, *bm_eos = nullptr, *bm_plen = nullptr, *bm_fan = nullptr; int4* bm_copies = nullptr;
+    hipGraphExec_t bgraph = nullptr;      // beam step: bookkeeping + forward + row statistics + select + KV suffix copies
+    int bg_B = -1, bg_W = 0, bg_K = 0, bg_neos = -1, bg_pad = 0, bg_max_new = 0, bg_px = 0; float bg_lp = 0.f;
     int h_ctx_hi = 0;              // longest context any slot can have reached (prefill length + decode steps issued)
     // ---- bookkeeping
     std::map<std::string, bool> loaded;
@@ -793,6 +800,8 @@ int sr_engine_destroy(sr_engine* e) {
     for (auto g : e->graph) if (g) (void)hipGraphExecDestroy(g);
     for (auto g : e->step_graph) if (g) (void)hipGraphExecDestroy(g);
     if (e->sgraph) (void)hipGraphExecDestroy(e->sgraph);
+    if (e->bgraph) (void)hipGraphExecDestroy(e->bgraph);
+    if (e->beam_mem) (void)hipFree(e->beam_mem);
     for (auto& r : e->rgraph) if (r.g) (void)hipGraphExecDestroy(r.g);
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     if (e->ev_copy) (void)hipEventDestroy(e->ev_copy);
@@ -1065,6 +1074,7 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
             h_slot[t] = slots[b];
             h_idx[t] = i;
         }
+        if (!limits) { e->pre_len[b] = S; e->pre_slot[b] = slots[b]; e->pre_pos[b] = (int)maxpos; }
         for (int q0 = 0; q0 < S; q0 += 64)
             h_work[n_work++] = AttnWork{t0 + q0, S, q0, slots[b] * KVH * c.max_ctx, (long long)slots[b] * KVH * 128 * c.max_ctx};
         h_last[b] = t0 + S - 1;
@@ -1488,6 +1498,183 @@ int sr_decode_sample(sr_engine* e, int B, int max_new, const int32_t* host_eos, 
     return 0;
 }
 
+// Beam search (HF _beam_search, do_sample=False, early_stopping=False) over the G prompts of the last sr_prefill, W beams each, entirely on
+// the device: the prompts are fanned out to W KV slots, and every step (one captured graph) feeds each row its chosen token (k_step),
+// runs the forward, the row statistics, the group select (next beams, finished list, early stop, slot map, copy list) and the KV suffix
+// copies.  The host polls the groups' stop flags every 16 steps and backtracks the parent / token trace once at the end.
+static int ensure_beam_mem(sr_engine* e) {
+    if (e->beam_mem) return 0;
+    const sr_config& c = e->c;
+    const size_t nb = beam_nb(c.t_vocab);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_part = take((size_t)MAXB * nb * (BEAM_MAXK + 1) * sizeof(BeamPart)), o_sc = take(MAXB * 4), o_tok = take(MAXB * 8),
+                 o_tr = take((size_t)c.max_new_tokens * MAXB * sizeof(BeamTrace)), o_fin = take(MAXB * sizeof(BeamFin)), o_fn = take(MAXB * 4),
+                 o_done = take(MAXB * 4), o_stop = take(MAXB * 4), o_eos = take(32 * 4), o_plen = take(MAXB * 4), o_fan = take(5 * MAXB * 4),
+                 o_cp = take(MAXB * sizeof(int4));
+    SR_TRY((int)hipMalloc(&e->beam_mem, off));
+    char* m = static_cast<char*>(e->beam_mem);
+    e->bm_part = reinterpret_cast<BeamPart*>(m + o_part); e->bm_scores = reinterpret_cast<float*>(m + o_sc);
+    e->bm_tok = reinterpret_cast<long long*>(m + o_tok); e->bm_trace = reinterpret_cast<BeamTrace*>(m + o_tr);
+    e->bm_fin = reinterpret_cast<BeamFin*>(m + o_fin); e->bm_fin_n = reinterpret_cast<int*>(m + o_fn); e->bm_done = reinterpret_cast<int*>(m + o_done);
+    e->bm_stop = reinterpret_cast<int*>(m + o_stop); e->bm_eos = reinterpret_cast<int*>(m + o_eos); e->bm_plen = reinterpret_cast<int*>(m + o_plen);
+    e->bm_fan = reinterpret_cast<int*>(m + o_fan); e->bm_copies = reinterpret_cast<int4*>(m + o_cp);
+    return 0;
+}
+
+static int suffix_nx(int max_new) { return std::min(16, std::max(1, (max_new * 16 + 128 * (max_new / 8 + 2)) / 1024)); }
+
+int sr_decode_beam(sr_engine* e, int G, int W, int R, int max_new, const int32_t* host_eos, int n_eos, int32_t pad_id, float length_penalty,
+                   int32_t* tokens_out, float* scores_out, int32_t* lengths_out, float* logits_trace, int32_t* beam_trace, int use_graph,
+                   void* stream, int* steps_done) {
+    enter(e);
+    if (!e || !tokens_out || !scores_out || !lengths_out) return fail(e, -22, "sr_decode_beam: null argument");
+    const sr_config& c = e->c;
+    if (e->rows_mode) return fail(e, -22, "sr_decode_beam: the engine is in continuous-batching mode");
+    if (W < 1 || W > BEAM_MAXW) return fail(e, -22, "sr_decode_beam: num_beams W=%d outside 1..%d", W, BEAM_MAXW);
+    if (R < 1 || R > W) return fail(e, -22, "sr_decode_beam: num_return_sequences R=%d outside 1..num_beams (%d)", R, W);
+    if (n_eos < 0 || n_eos > 32 || (n_eos && !host_eos)) return fail(e, -22, "sr_decode_beam: n_eos=%d out of range", n_eos);
+    const int K = std::max(2, 1 + n_eos) * W;
+    if (K > BEAM_MAXK) return fail(e, -22, "sr_decode_beam: K = max(2, 1 + n_eos) * W = %d candidates exceed %d", K, BEAM_MAXK);
+    if (G < 1 || G != e->prefilled_B) return fail(e, -22, "sr_decode_beam: G=%d but %d prompts were prefilled", G, e->prefilled_B);
+    const int B = G * W;
+    if (B > c.max_batch) return fail(e, -22, "sr_decode_beam: G*W = %d rows exceed max_batch %d", B, c.max_batch);
+    if (max_new < 1 || max_new > c.max_new_tokens) return fail(e, -22, "sr_decode_beam: max_new=%d outside 1..%d", max_new, c.max_new_tokens);
+    if (e->h_ctx_hi + max_new > c.max_ctx)
+        return fail(e, -22, "sr_decode_beam: context %d + %d new tokens exceeds max_ctx %d", e->h_ctx_hi, max_new, c.max_ctx);
+    if (c.t_vocab < K) return fail(e, -22, "sr_decode_beam: vocabulary %d smaller than K=%d", c.t_vocab, K);
+    SR_TRY(ensure_beam_mem(e));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t V = c.t_vocab;
+    // ---- rows: group g's beam 0 keeps the prompt's KV slot, the others take free slots; every row starts at the prompt's state
+    std::vector<int> used(e->n_slots, 0), rslot(B), st(5 * MAXB, 0), fan(5 * MAXB, 0), plen(MAXB, 0);
+    for (int g = 0; g < G; ++g) used[e->pre_slot[g]] = 1;
+    for (int g = 0, f = 0; g < G; ++g) {
+        plen[g] = e->pre_len[g];
+        for (int j = 0; j < W; ++j) {
+            int sl = e->pre_slot[g];
+            if (j) { while (used[f]) ++f; used[f] = 1; sl = f; fan[g * (W - 1) + j - 1] = sl; }
+            const int r = g * W + j;
+            rslot[r] = sl; st[r] = e->pre_len[g]; st[MAXB + r] = e->pre_pos[g]; st[2 * MAXB + r] = sl;
+        }
+        int* gr = fan.data() + MAXB + 4 * g;        // fan-out group: [src | L | first destination | destinations]
+        gr[0] = e->pre_slot[g]; gr[1] = e->pre_len[g]; gr[2] = g * (W - 1); gr[3] = W - 1;
+    }
+    std::vector<float> sc0(B);
+    for (int r = 0; r < B; ++r) sc0[r] = (r % W) ? -1.0e9f : 0.0f;
+    std::vector<int> stop0(G, -1);
+    SR_TRY((int)hipMemcpyAsync(e->d_ctx_len, st.data(), MAXB * 4, hipMemcpyHostToDevice, s));
+    SR_TRY((int)hipMemcpyAsync(e->d_pos, st.data() + MAXB, MAXB * 4, hipMemcpyHostToDevice, s));
+    SR_TRY((int)hipMemcpyAsync(e->d_slots, st.data() + 2 * MAXB, MAXB * 4, hipMemcpyHostToDevice, s));
+    SR_TRY((int)hipMemsetAsync(e->d_finished, 0, MAXB * 4, s));
+    SR_TRY((int)hipMemsetAsync(e->d_step, 0, MAXB * 4, s));
+    SR_TRY((int)hipMemsetAsync(e->d_row_limit, 0x7f, MAXB * 4, s));
+    SR_TRY((int)hipMemsetAsync(e->d_ngen, 0, MAXB * 4, s));
+    SR_TRY((int)hipMemcpyAsync(e->bm_scores, sc0.data(), B * 4, hipMemcpyHostToDevice, s));
+    SR_TRY((int)hipMemsetAsync(e->bm_fin_n, 0, MAXB * 4, s));
+    SR_TRY((int)hipMemsetAsync(e->bm_done, 0, MAXB * 4, s));
+    SR_TRY((int)hipMemcpyAsync(e->bm_stop, stop0.data(), G * 4, hipMemcpyHostToDevice, s));
+    SR_TRY((int)hipMemsetAsync(e->bm_trace, 0xff, (size_t)max_new * B * sizeof(BeamTrace), s));
+    if (n_eos) SR_TRY((int)hipMemcpyAsync(e->bm_eos, host_eos, n_eos * 4, hipMemcpyHostToDevice, s));
+    SR_TRY((int)hipMemcpyAsync(e->bm_plen, plen.data(), MAXB * 4, hipMemcpyHostToDevice, s));
+    // the prompt's logits row g -> rows g*W .. g*W+W-1 (descending g: a source row is read before any copy can overwrite it)
+    for (int g = G - 1; g >= 0; --g)
+        for (int j = 0; j < W; ++j)
+            if (g * W + j != g)
+                SR_TRY((int)hipMemcpyAsync(e->d_logits + (size_t)(g * W + j) * V, e->d_logits + (size_t)g * V, V * 4, hipMemcpyDeviceToDevice, s));
+    if (W > 1) {
+        int max_L = 0;
+        for (int g = 0; g < G; ++g) max_L = std::max(max_L, e->pre_len[g]);
+        SR_TRY((int)hipMemcpyAsync(e->bm_fan, fan.data(), 5 * MAXB * 4, hipMemcpyHostToDevice, s));
+        KvFanoutArgs fa{e->kcache, e->vtcache, (long long)e->kv_layer_elems, c.t_layers, c.t_kv_heads, c.max_ctx, e->bm_fan, 0, 0, 0,
+                        e->bm_fan + MAXB, G, max_L};
+        SR_TRY(launch_kv_fanout(s, fa));
+    }
+    e->h_ctx_hi += max_new;
+    e->prefilled_B = 0;            // the rows now hold beams: a new prefill is needed before the next decode
+    BeamArgs ba{e->d_logits, (int)V, G, W, K, beam_nb((int)V), e->bm_part, e->bm_scores, e->bm_tok, e->bm_trace, B, e->bm_fin, e->bm_fin_n,
+                e->bm_done, e->bm_stop, e->bm_eos, n_eos, pad_id, max_new, length_penalty, e->d_step, 0, e->d_slots, e->d_ctx_len, e->bm_plen,
+                e->bm_copies};
+    KvSuffixArgs ka{e->kcache, e->vtcache, (long long)e->kv_layer_elems, c.t_layers, c.t_kv_heads, c.max_ctx, e->bm_copies, B, suffix_nx(max_new)};
+    auto select = [&](hipStream_t q) -> int {
+        SR_TRY(launch_beam_rowstats(q, ba));
+        SR_TRY(launch_beam_select(q, ba));
+        SR_TRY(launch_kv_suffix(q, ka));
+        return 0;
+    };
+    auto enqueue = [&](hipStream_t q) -> int {     // one step: feed the chosen tokens, forward, select the next ones
+        if (int rc = enqueue_step(e, B, 0, pad_id, nullptr, q, e->bm_tok)) return rc;
+        if (int rc = enqueue_decode_forward(e, B, q)) return rc;
+        return select(q);
+    };
+    const bool graph_ok = use_graph && !logits_trace;
+    if (graph_ok && (e->bgraph == nullptr || e->bg_B != B || e->bg_W != W || e->bg_K != K || e->bg_neos != n_eos || e->bg_pad != pad_id ||
+                     e->bg_max_new != max_new || e->bg_lp != length_penalty || e->bg_px != e->px_mode)) {
+        if (e->bgraph) { (void)hipGraphExecDestroy(e->bgraph); e->bgraph = nullptr; }
+        hipGraph_t g = nullptr;
+        SR_TRY((int)hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
+        int rc = enqueue(e->cap_stream);
+        hipError_t er = hipStreamEndCapture(e->cap_stream, &g);
+        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+        SR_TRY((int)er);
+        er = hipGraphInstantiate(&e->bgraph, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        SR_TRY((int)er);
+        e->bg_B = B; e->bg_W = W; e->bg_K = K; e->bg_neos = n_eos; e->bg_pad = pad_id; e->bg_max_new = max_new; e->bg_lp = length_penalty;
+        e->bg_px = e->px_mode;
+    }
+    if (logits_trace) SR_TRY((int)hipMemcpyAsync(logits_trace, e->d_logits, B * V * 4, hipMemcpyDeviceToDevice, s));
+    if (int rc = select(s)) return rc;             // step 0, from the prompts' logits
+    int done = 1;
+    std::vector<int> gd(G);
+    for (int i = 1; i < max_new; ++i) {
+        if (graph_ok) SR_TRY((int)hipGraphLaunch(e->bgraph, s));
+        else {
+            if (int rc = enqueue_step(e, B, 0, pad_id, nullptr, s, e->bm_tok)) return rc;
+            if (int rc = enqueue_decode_forward(e, B, s)) return rc;
+            if (logits_trace) SR_TRY((int)hipMemcpyAsync(logits_trace + (size_t)i * B * V, e->d_logits, B * V * 4, hipMemcpyDeviceToDevice, s));
+            if (int rc = select(s)) return rc;
+        }
+        done = i + 1;
+        if ((i % 16) == 15) {                      // early exit once every group has stopped
+            SR_TRY((int)hipMemcpyAsync(gd.data(), e->bm_done, G * 4, hipMemcpyDeviceToHost, s));
+            SR_TRY((int)hipStreamSynchronize(s));
+            bool all = true;
+            for (int g = 0; g < G; ++g) all &= gd[g] != 0;
+            if (all) break;
+        }
+    }
+    // ---- the finished lists and the trace -> host; backtrack the R best hypotheses of every group
+    std::vector<BeamFin> fin(B);
+    std::vector<int> fin_n(G);
+    std::vector<BeamTrace> tr((size_t)done * B);
+    SR_TRY((int)hipMemcpyAsync(fin.data(), e->bm_fin, B * sizeof(BeamFin), hipMemcpyDeviceToHost, s));
+    SR_TRY((int)hipMemcpyAsync(fin_n.data(), e->bm_fin_n, G * 4, hipMemcpyDeviceToHost, s));
+    SR_TRY((int)hipMemcpyAsync(tr.data(), e->bm_trace, tr.size() * sizeof(BeamTrace), hipMemcpyDeviceToHost, s));
+    if (beam_trace) SR_TRY((int)hipMemcpyAsync(beam_trace, e->bm_trace, (size_t)max_new * B * sizeof(BeamTrace), hipMemcpyDeviceToDevice, s));
+    SR_TRY((int)hipStreamSynchronize(s));
+    for (int g = 0; g < G; ++g) {
+        if (fin_n[g] < R) return fail(e, -5, "sr_decode_beam: group %d finished %d hypotheses, %d requested", g, fin_n[g], R);
+        for (int r = 0; r < R; ++r) {
+            const BeamFin& f = fin[g * W + r];
+            int32_t* out = tokens_out + ((size_t)g * R + r) * max_new;
+            for (int k = 0; k < max_new; ++k) out[k] = pad_id;
+            if (f.step < 0 || f.step >= done) return fail(e, -5, "sr_decode_beam: corrupt finished entry (step %d)", f.step);
+            out[f.step] = f.token;
+            for (int k = f.step - 1, b = f.parent; k >= 0; --k) {
+                if (b < 0 || b >= W) return fail(e, -5, "sr_decode_beam: corrupt trace (step %d beam %d)", k, b);
+                const BeamTrace& t = tr[(size_t)k * B + g * W + b];
+                out[k] = t.token;
+                b = t.parent;
+            }
+            scores_out[g * R + r] = f.score;
+            lengths_out[g * R + r] = f.step + 1;
+        }
+    }
+    if (steps_done) *steps_done = done;
+    return 0;
+}
+
 int sr_rows_step(sr_engine* e, int n_steps, const int32_t* host_eos, int n_eos, int32_t pad_id, void* stream) {
     enter(e);
     if (!e || !e->rows_mode) return fail(e, -22, "sr_rows_step: call sr_rows_begin first");
@@ -1794,6 +1981,39 @@ int sr_op_kv_fanout(void* kcache, void* vtcache, int n_layers, int64_t layer_str
     KvFanoutArgs a{static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vtcache), (long long)layer_stride_elems, n_layers, n_kv_heads, max_ctx,
                    dev_dst_slots, src_slot, L, d, nullptr, 0, 0};
     SR_WRAP(launch_kv_fanout((hipStream_t)stream, a));
+}
+int sr_op_kv_suffix_copy(void* kcache, void* vtcache, int n_layers, int64_t layer_stride_elems, int n_kv_heads, int max_ctx,
+                         const int32_t* dev_copies, int n, int max_len, void* stream) {
+    if (!kcache || !vtcache || !dev_copies || n < 0 || n > 65535 || max_len < 0) return fail(nullptr, -22, "sr_op_kv_suffix_copy: bad argument");
+    KvSuffixArgs a{static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vtcache), (long long)layer_stride_elems, n_layers, n_kv_heads, max_ctx,
+                   reinterpret_cast<const int4*>(dev_copies), n, suffix_nx(max_len)};
+    SR_WRAP(launch_kv_suffix((hipStream_t)stream, a));
+}
+int sr_op_beam_select(const float* logits, int G, int W, int V, const int32_t* host_eos, int n_eos, int step, int max_new, float length_penalty,
+                      int32_t pad_id, float* dev_scores, void* dev_fin, int32_t* dev_fin_n, int32_t* dev_done, int32_t* dev_trace,
+                      int64_t* dev_next_tok, void* stream) {
+    const int K = std::max(2, 1 + n_eos) * W;
+    if (!logits || !dev_scores || !dev_fin || !dev_fin_n || !dev_done || !dev_trace || !dev_next_tok || G < 1 || W < 1 || W > BEAM_MAXW ||
+        G * W > MAXB || n_eos < 0 || n_eos > 32 || K > BEAM_MAXK || V < K || step < 0 || step >= max_new)
+        return fail(nullptr, -22, "sr_op_beam_select: bad argument (G=%d W=%d V=%d n_eos=%d step=%d max_new=%d)", G, W, V, n_eos, step, max_new);
+    hipStream_t s = (hipStream_t)stream;
+    const int NB = beam_nb(V);
+    void* scratch = nullptr;
+    const size_t part_bytes = (size_t)G * W * NB * (K + 1) * sizeof(BeamPart);
+    if (hipMalloc(&scratch, part_bytes + 64 * 4 + MAXB * 4) != hipSuccess) return fail(nullptr, -12, "sr_op_beam_select: out of memory");
+    int* eos = reinterpret_cast<int*>(static_cast<char*>(scratch) + part_bytes);
+    int rc = 0;
+    if (n_eos) rc = (int)hipMemcpyAsync(eos, host_eos, n_eos * 4, hipMemcpyHostToDevice, s);
+    BeamArgs a{logits, V, G, W, K, NB, static_cast<BeamPart*>(scratch), dev_scores, reinterpret_cast<long long*>(dev_next_tok),
+               reinterpret_cast<BeamTrace*>(dev_trace), G * W, static_cast<BeamFin*>(dev_fin), dev_fin_n, dev_done, eos + 64,
+               eos, n_eos, pad_id, max_new, length_penalty, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+    a.step = step;                // (the stop step goes to scratch: the op reports the stop through dev_done)
+    if (!rc) rc = launch_beam_rowstats(s, a);
+    if (!rc) rc = launch_beam_select(s, a);
+    if (!rc) rc = (int)hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    if (rc) return fail(nullptr, rc, "sr_op_beam_select failed with %d", rc);
+    return 0;
 }
 int sr_op_argmax(const float* logits, int rows, int V, int32_t* out_idx, void* stream) {
     SR_WRAP(launch_argmax((hipStream_t)stream, logits, rows, V, out_idx));

@@ -232,6 +232,34 @@ struct KvFanoutArgs {
     const int* groups; int n_groups, max_L;  // ... or n_groups of them: [src | L | first index into dst | d] each (device), max_L >= every L
 };
 int launch_kv_fanout(hipStream_t s, const KvFanoutArgs& a);
+// ------------------------------------------------------------------ beam.hip
+// deterministic beam search (HF _beam_search, do_sample=False): G groups x W beams = B rows, group g owns rows g*W .. g*W+W-1
+constexpr int RS_CH = 4096;                  // logits per k_beam_rowstats block
+constexpr int BEAM_MAXW = 8, BEAM_MAXK = 64;   // beams per group; candidates per group and step (K = max(2, 1 + n_eos) * W)
+inline int beam_nb(int V) { return (V + RS_CH - 1) / RS_CH; }
+struct BeamPart { float v; int i; };          // chunk partials: [row][chunk][K + 1] = (max, sum exp bits) then the chunk's top-K (logit, token)
+struct BeamTrace { int parent, token; };      // [step][row]: the beam of the previous step a running beam continues, and its new token
+struct BeamFin { float score; int step, parent, token; };   // finished hypothesis: cum / len^lp, the step of its last token, parent beam, token
+struct BeamArgs {
+    const float* logits; int V, G, W, K, NB;  // logits [B][V]
+    BeamPart* part;                           // [B][NB][K + 1]
+    float* scores;                            // [B] running cumulative log-probs (in / out)
+    long long* next_tok;                      // [B] token each row feeds next (k_step's `chosen`)
+    BeamTrace* trace; int trace_ld;           // [step][trace_ld]
+    BeamFin* fin; int* fin_n; int* done; int* stop_step;   // [B] (W per group, best first), [G], [G], [G]
+    const int* eos; int n_eos, pad_id, max_new; float lp;
+    const int* step_ctr; int step;            // this step's index: step_ctr[g * W] (k_step's per-row counter) or `step` when null
+    int* slots; const int* ctx_len; const int* prompt_len; int4* copies;   // optional KV reorder: row -> slot map (in / out), [B] ctx, [G],
+                                                                           // copy list [B] (src slot, dst slot, L0, L1), unused entries src -1
+};
+int launch_beam_rowstats(hipStream_t s, const BeamArgs& a);
+int launch_beam_select(hipStream_t s, const BeamArgs& a);
+// positions [L0, L1) of slot src -> slot dst for every entry (src, dst, L0, L1) of `copies` (src < 0: skipped), every layer, both caches
+struct KvSuffixArgs {
+    bf16_t* kcache; bf16_t* vtcache; long long layer_stride; int n_layers, n_kvh, max_ctx;
+    const int4* copies; int n, nx;            // entries; blocks per (layer, kv head), each strides over the chunks
+};
+int launch_kv_suffix(hipStream_t s, const KvSuffixArgs& a);
 int launch_rows_abort(hipStream_t s, const unsigned row_mask[4], int* finished);      // finished[b] = 1 for every bit b of the 128-bit row mask
 // ------------------------------------------------------------------ sample.hip
 struct SampleArgs {

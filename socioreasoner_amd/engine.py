@@ -206,6 +206,31 @@ class Engine:
         self.steps_done = done.value
         return toks
 
+    def decode_beam(self, num_beams: int, max_new: int, num_return_sequences: int = 1, length_penalty: float = 1.0, eos: Sequence[int] = (),
+                    pad_id: int = 0, trace: bool = False, use_graph: bool = True):
+        """Beam search on the device (HF _beam_search, do_sample=False, early_stopping=False) for the G prompts of the last prefill, W =
+        num_beams beams each (G * W <= max_batch).  -> (tokens int32 [G, R, max_new] with eos included then pad, scores float32 [G, R],
+        lengths int32 [G, R]), the R = num_return_sequences best finished hypotheses of every prompt, best first.  trace=True (eager
+        launches) also keeps self.beam_logits float32 [max_new, G*W, V] and self.beam_trace int32 [max_new, G*W, 2] (parent beam, token)."""
+        G, W, R = self._last_B, int(num_beams), int(num_return_sequences)
+        toks = np.empty((G, R, max_new), dtype=np.int32)
+        scores = np.empty((G, R), dtype=np.float32)
+        lens = np.empty((G, R), dtype=np.int32)
+        eos_a = np.asarray(list(eos), dtype=np.int32)
+        lg = torch.empty(max_new, G * W, self.geom.text.vocab_size, dtype=torch.float32, device=self.device) if trace else None
+        bt = torch.empty(max_new, G * W, 2, dtype=torch.int32, device=self.device) if trace else None
+        done = C.c_int(0)
+        L.check(self.lib.sr_decode_beam(self._h, G, W, R, int(max_new), eos_a.ctypes.data_as(L._i32p) if len(eos_a) else None, len(eos_a),
+                                        int(pad_id), C.c_float(length_penalty), toks.ctypes.data_as(L._i32p), C.c_void_p(scores.ctypes.data),
+                                        lens.ctypes.data_as(L._i32p), C.c_void_p(lg.data_ptr()) if trace else None,
+                                        C.c_void_p(bt.data_ptr()) if trace else None, 1 if use_graph and not trace else 0, self._s(),
+                                        C.byref(done)), self._h, "sr_decode_beam")
+        self.steps_done = done.value
+        self._last_B = 0
+        if trace:
+            self.beam_logits, self.beam_trace = lg, bt
+        return torch.from_numpy(toks), torch.from_numpy(scores), torch.from_numpy(lens)
+
     def forward_logits(self, ids: Sequence[np.ndarray], pos3: Sequence[np.ndarray], image_embeds: torch.Tensor | None = None):
         """Teacher-forced forward: float32 logits [n_tok, V] for every position of the packed sequences."""
         B = len(ids)

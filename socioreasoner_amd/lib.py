@@ -58,6 +58,7 @@ SIGNATURES = {
     "sr_admit_stage": (C.c_int, [_vp, _i64p, _i64p, _i32p, _i32p, _i32p, _i, _vp, _i, _vp, _vp]),
     "sr_admit_commit": (C.c_int, [_vp, _i32p, _i, _vp]),
     "sr_admit_fanout": (C.c_int, [_vp, _i64p, _i64p, _i32p, _i32p, _i32p, _i32p, _i, _vp, _i, _vp, _vp]),
+    "sr_decode_beam": (C.c_int, [_vp, _i, _i, _i, _i, _i32p, _i, C.c_int32, C.c_float, _i32p, _vp, _i32p, _vp, _vp, _i, _vp, C.POINTER(C.c_int)]),
     "sr_admit_stage_fanout": (C.c_int, [_vp, _i64p, _i64p, _i32p, _i32p, _i32p, _i32p, _i, _vp, _i, _vp, _vp]),
     "sr_rows_step": (C.c_int, [_vp, _i, _i32p, _i, C.c_int32, _vp]),
     "sr_rows_set_cus": (C.c_int, [_vp, _i, _vp]),
@@ -106,6 +107,8 @@ SIGNATURES = {
     "sr_op_resid_rmsnorm": (C.c_int, [_vp, _vp, _i, _vp, _vp, _i, _i, C.c_float, _vp]),
     "sr_op_argmax": (C.c_int, [_vp, _i, _i, _vp, _vp]),
     "sr_op_kv_fanout": (C.c_int, [_vp, _vp, _i, C.c_int64, _i, _i, _i, _vp, _i, _i, _vp]),
+    "sr_op_kv_suffix_copy": (C.c_int, [_vp, _vp, _i, C.c_int64, _i, _i, _vp, _i, _i, _vp]),
+    "sr_op_beam_select": (C.c_int, [_vp, _i, _i, _i, _i32p, _i, _i, _i, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_switches_reload": (C.c_int, []),
 }
 
