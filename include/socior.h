@@ -226,6 +226,35 @@ int sr_admit_stage_fanout(sr_engine* e, const int64_t* host_ids, const int64_t* 
 int sr_admit_fanout(sr_engine* e, const int64_t* host_ids, const int64_t* host_pos3, const int32_t* host_seq_lens,
                     const int32_t* host_fanout, const int32_t* host_rows, const int32_t* host_max_new, int n,
                     const void* dev_image_embeds, int n_image_rows, float* dev_logits_out, void* stream);
+/* Per-request sampling in the continuous batcher: one parameter entry per staged SEQUENCE (prompt-major, as the fan-out's slots). */
+typedef struct sr_sampling {
+    float temperature;          /* 0: greedy -- the arg-max of the (penalised) logits, ties to the lowest id; < 0 refused */
+    int32_t top_k;              /* <= 1024 (<= 0: no top-k bound) */
+    float top_p;                /* (0, 1] */
+    float repetition_penalty;   /* > 0, 1 = none: l > 0 ? l / rp : l * rp on every token of the prompt and of the generated sequence */
+    uint32_t seed;              /* the draws of step s use the counter-based key (seed, stream, s) */
+    int32_t stream;             /* >= 0: the stream id (e.g. the fork index: tokens that depend on no row, slot, admission order or neighbour);
+                                 * < 0: the row's stream of sr_rows_sampling (seed = its seed gives that path's tokens exactly) */
+} sr_sampling;
+/*   sr_admit_stage_sampling / sr_admit_sampling : sr_admit_stage_fanout / sr_admit_fanout (host_fanout may be null: one sequence per prompt)
+ *                   with host_sampling[sum of fanout]: each sequence draws its first token under its own entry, its KV slot's
+ *                   repetition-penalty bitmap is cleared and marked with its prompt (forks: each slot gets the prompt), and sr_admit_commit
+ *                   installs the entries with the rows.  The first call allocates the per-row state outside the workspace (parameter table
+ *                   + one bitmap of ceil(V / 32) words per KV slot); from then on EVERY admission stages entries (the plain calls: the
+ *                   sr_rows_sampling configuration, keyed by the row).  Refused by name: temperature < 0, top_k > 1024, top_p outside
+ *                   (0, 1], repetition_penalty <= 0.
+ *   sr_rows_per_row : on = 1: sr_rows_step replays the per-row step -- greedy, top-k, unbounded nucleus and penalised rows in one captured
+ *                   graph (the consumed tokens are marked in their slot's bitmap, k_sample skips the unbounded rows, k_sample_full the
+ *                   others) -- instead of the shared greedy / sampled step; 0 = back to the shared step.  With every entry equal to the
+ *                   shared configuration both give the same tokens, so the switch may happen between any two steps. */
+int sr_admit_stage_sampling(sr_engine* e, const int64_t* host_ids, const int64_t* host_pos3, const int32_t* host_seq_lens,
+                            const int32_t* host_fanout, const int32_t* host_kv_slots, const int32_t* host_max_new,
+                            const sr_sampling* host_sampling, int n, const void* dev_image_embeds, int n_image_rows, float* dev_logits_out,
+                            void* stream);
+int sr_admit_sampling(sr_engine* e, const int64_t* host_ids, const int64_t* host_pos3, const int32_t* host_seq_lens,
+                      const int32_t* host_fanout, const int32_t* host_rows, const int32_t* host_max_new, const sr_sampling* host_sampling,
+                      int n, const void* dev_image_embeds, int n_image_rows, float* dev_logits_out, void* stream);
+int sr_rows_per_row(sr_engine* e, int on, void* stream);
 int sr_rows_step(sr_engine* e, int n_steps, const int32_t* host_eos, int n_eos, int32_t pad_id, void* stream);
 int sr_rows_poll(sr_engine* e, int32_t* host_finished, int32_t* host_steps, void* stream);
 int sr_rows_read(sr_engine* e, int row, int32_t* dev_tokens_out, int n, void* stream);

@@ -335,16 +335,20 @@ class Mi355xStrategy(InferenceStrategy):
         if W > 1:
             self._generate_beam(prepared, results, gc, W, n, eos, pad, max_new)
             i = B
-        elif greedy or (on_device and rp1):
+        elif greedy or on_device or sampling.is_greedy(gc):
             # the stages are decoupled: the scheduler admits the prompts in capacity-sized groups (ViT + prefill into free KV rows)
             # and ALL filled rows decode together -- a batch larger than one admission, or than max_batch, still decodes at full
             # width, and rows freed by short answers are refilled at once (socioreasoner_amd/serving.py).  Sampled n > 1: one request of n
-            # sequences per prompt (chunks of at most max_batch), prefilled once and fanned out into n rows by the engine
+            # sequences per prompt (chunks of at most max_batch), prefilled once and fanned out into n rows by the engine.  A repetition
+            # penalty rides on the requests' own parameters (the per-row step); greedy with a penalty is the arg-max of the penalised logits
             from socioreasoner_amd.serving import ContinuousBatcher, Request
-            smp = None if greedy else {"temperature": float(gc.get("temperature", 1.0)), "top_k": int(tk), "top_p": float(gc.get("top_p", 1.0) or 1.0),
-                                       "seed": int(gc.get("seed", 0) or 0) * 1000003 + 7919 * int(getattr(self.worker, "rank", 0) or 0)}
+            g0 = sampling.is_greedy(gc)
+            smp = None if g0 else {"temperature": float(gc.get("temperature", 1.0)), "top_k": int(tk), "top_p": float(gc.get("top_p", 1.0) or 1.0),
+                                   "seed": int(gc.get("seed", 0) or 0) * 1000003 + 7919 * int(getattr(self.worker, "rank", 0) or 0)}
+            own = None if rp1 else dict({k: v for k, v in (smp or {"temperature": 0.0}).items() if k != "seed"},
+                                        repetition_penalty=float(gc.get("repetition_penalty", 1.0)))
             reqs, owner = [], []
-            fan = 1 if greedy else n                   # greedy n > 1: the n answers are one answer, copied below
+            fan = 1 if g0 else n                       # greedy n > 1: the n answers are one answer, copied below
             mb = self.engine.cfg.max_batch
             for k in range(B):
                 ids_k, pos_k, ims_k, grids_k = prepared[k]
@@ -352,7 +356,8 @@ class Mi355xStrategy(InferenceStrategy):
                 if room < 1:
                     raise ValueError(f"prompt of {len(ids_k)} tokens leaves no room in max_ctx {self.engine.cfg.max_ctx}")
                 for c0 in range(0, fan, mb):
-                    reqs.append(Request(ids=ids_k, pos3=pos_k, max_new=max(1, min(max_new, room)), images=ims_k, grids=grids_k, n=min(mb, fan - c0)))
+                    reqs.append(Request(ids=ids_k, pos3=pos_k, max_new=max(1, min(max_new, room)), images=ims_k, grids=grids_k, n=min(mb, fan - c0),
+                                        sampling=own))
                     owner.append(k)
             t_run0 = _time.perf_counter()
             cb = ContinuousBatcher(self.engine, eos, pad, sampling=smp, overlap=self.overlap)
@@ -369,10 +374,10 @@ class Mi355xStrategy(InferenceStrategy):
                     row = [int(t) for t in row]
                     cut = next((j + 1 for j, t in enumerate(row) if t in eos), len(row))
                     results[k].append(row[:cut])
-            if greedy:
+            if g0:
                 results = [rs * n for rs in results]
             i = B
-        while i < B:                                  # static batches (repetition penalty, top-k above 1024)
+        while i < B:                                  # static batches (sampling with top-k above 1024)
             grp, ntok, npatch = [], 0, 0
             while i < B and len(grp) < self.max_batch:
                 ids_i, _, _, grids = prepared[i]
@@ -489,14 +494,17 @@ class Mi355xStrategy(InferenceStrategy):
 
     def start_server(self, data: DataProto, request_complete_callback):
         """Request-level serving (reference vllm_strategy.py:156-205): ADD / ABORT / STOP commands arrive through the queue
-        while the loop runs; greedy requests and sampling requests with a top-k bound are served by CONTINUOUS batching
-        (socioreasoner_amd.serving: admit on finish, one graph replay per token for all rows, the draw inside the graph; a sampled request
-        with num_return_sequences n > 1 is admitted once and fanned out into n rows); anything else (repetition penalty, top-k above 1024,
-        n above the engine's rows) in engine-sized static batches.  Each request is reported through the callback the moment its last
-        sequence ends, with its n token lists in output_token_ids."""
+        while the loop runs; greedy requests and sampling requests with a top-k bound of at most 1024 (any repetition penalty) are served by
+        CONTINUOUS batching (socioreasoner_amd.serving: admit on finish, one graph replay per token for all rows, the draw inside the graph; a
+        sampled request with num_return_sequences n > 1 is admitted once and fanned out into n rows).  The batcher's shared configuration is
+        that of the request that opened it; a request with other sampling parameters, or a repetition penalty, joins the running rows under
+        its own parameters (Request.sampling: its seed gives the streams (seed, fork); without a seed the batcher derives one per request, so
+        two such requests with the same prompt draw differently).  Static batches, after the running rows have drained, remain for: an eos
+        set or pad id other than the running batcher's, num_beams > 1, a top-k bound above 1024 and n above the engine's rows.  Each request
+        is reported through the callback the moment its last sequence ends, with its n token lists in output_token_ids."""
         from socioreasoner_amd.serving import ContinuousBatcher, Request
         self.running = True
-        batcher, bkey = None, None
+        batcher, bkey, bdkey = None, None, None
         sampled: List[DataProto] = []
         stop = False
         last_cmd = 0.0
@@ -514,13 +522,13 @@ class Mi355xStrategy(InferenceStrategy):
                 name = getattr(command, "name", command)
                 if name == "ADD":
                     gc = dict(req.meta_info.get("generation_config") or {})
-                    rp1 = float(gc.get("repetition_penalty", 1.0) or 1.0) == 1.0
                     greedy = sampling.is_greedy(gc)
                     tk = gc.get("top_k", -1)
                     tk = -1 if tk is None else int(tk)
                     dev_sampling = not greedy and tk <= 1024 and float(gc.get("temperature", 1.0)) > 1e-5
                     n_req = int(gc.get("num_return_sequences", 1) or 1)
-                    rows_ok = (hasattr(self.engine, "rows_begin") and rp1 and (greedy or dev_sampling)
+                    rp = float(gc.get("repetition_penalty", 1.0) or 1.0)
+                    rows_ok = (hasattr(self.engine, "rows_begin") and (greedy or dev_sampling) and rp > 0
                                and n_req <= getattr(getattr(self.engine, "cfg", None), "max_batch", 1)
                                and int(gc.get("num_beams", 1) or 1) == 1)          # beam search: the static path (generate's beam branch)
                     if not rows_ok:
@@ -529,15 +537,24 @@ class Mi355xStrategy(InferenceStrategy):
                         eos = gc.get("eos_token_id") or [self.tokenizer.eos_token_id]
                         eos = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos])]
                         pad = int(gc.get("pad_token_id", self.tokenizer.pad_token_id))
+                        base_seed = int(gc.get("seed", 0) or 0) * 1000003 + 7919 * int(getattr(self.worker, "rank", 0) or 0)      # (as generate())
                         smp = None if greedy else {"temperature": float(gc.get("temperature", 1.0)), "top_k": int(tk),
-                                                   "top_p": float(gc.get("top_p", 1.0) or 1.0),
-                                                   "seed": int(gc.get("seed", 0) or 0) * 1000003 + 7919 * int(getattr(self.worker, "rank", 0) or 0)}      # (as generate())
-                        key = (tuple(eos), pad, None if smp is None else tuple(sorted(smp.items())))
-                        if batcher is None or (key != bkey and batcher.idle()):
-                            batcher, bkey = ContinuousBatcher(self.engine, eos, pad, sampling=smp, overlap=self.overlap), key
+                                                   "top_p": float(gc.get("top_p", 1.0) or 1.0), "seed": base_seed}
+                        key = (tuple(eos), pad)
+                        dkey = None if smp is None else tuple(sorted(smp.items()))
+                        # a new batcher (its shared configuration = this request's) only when none runs; a running one takes requests with other
+                        # sampling parameters into its rows, each under its own parameters (the per-row step)
+                        if batcher is None or (batcher.idle() and (key, dkey) != (bkey, bdkey)):
+                            batcher, bkey, bdkey = ContinuousBatcher(self.engine, eos, pad, sampling=smp, overlap=self.overlap), key, dkey
                         if key != bkey:
-                            sampled.append(req)          # different stop set / sampling parameters while rows are running: static path
+                            sampled.append(req)          # a different stop set / pad id while rows are running: static path
                         else:
+                            own = None
+                            if dkey != bdkey or rp != 1.0:
+                                own = {"temperature": 0.0 if greedy else float(gc.get("temperature", 1.0)), "top_k": int(tk),
+                                       "top_p": float(gc.get("top_p", 1.0) or 1.0), "repetition_penalty": rp}
+                                if gc.get("seed") is not None:      # its own seed: streams (seed, fork); without one the batcher derives a seed per request
+                                    own["seed"] = base_seed
                             if req.meta_info.get("_prepared") is not None:          # done by add_request on the caller's thread
                                 ids, pos3, ims, grids = req.meta_info.pop("_prepared")
                             else:
@@ -552,7 +569,7 @@ class Mi355xStrategy(InferenceStrategy):
                                 raise ValueError(f"prompt of {len(ids)} tokens leaves no room in max_ctx {self.engine.cfg.max_ctx}")
                             max_new = max(1, min(int(gc["max_new_tokens"]), self.engine.cfg.max_new_tokens, room))
                             batcher.submit(Request(ids=ids, pos3=pos3, max_new=max_new, images=ims, grids=grids, tag=req,
-                                                   n=1 if greedy else n_req))          # (greedy: the n answers are one answer)
+                                                   n=1 if greedy else n_req, sampling=own))          # (greedy: the n answers are one answer)
                 elif name == "ABORT":
                     rid = req.meta_info["request_id"]
                     sampled = [p for p in sampled if p.meta_info.get("request_id") != rid]

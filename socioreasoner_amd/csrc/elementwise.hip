@@ -358,10 +358,15 @@ __global__ void k_admit_rows(AdmitArgs a) {
         a.step[r] = 0;
         a.n_gen[r] = 0;
         a.row_limit[r] = a.limit[i];
+        if (a.sampled) a.sampled[r] = a.first_pick ? a.first_pick[i] : a.first_tok[i];
+        // the staged entry (RP_ROW_STREAM stays: the row's draws are then keyed by the row, as sr_rows_sampling keys them)
+        if (a.row_params) a.row_params[r] = a.stage_params ? a.stage_params[i] : a.dflt;
     }
+    // (per-row sampling: the drawn first token, so that the greedy graph and the sampled graphs both consume it)
+    const int first = a.first_pick ? (int)a.first_pick[i] : a.first_tok[i];
     for (int k = threadIdx.x; k < a.n_part; k += blockDim.x) {
         a.amax_val[(size_t)r * a.n_part + k] = k == 0 ? 0.0f : -INFINITY;
-        a.amax_idx[(size_t)r * a.n_part + k] = k == 0 ? a.first_tok[i] : 0x7fffffff;
+        a.amax_idx[(size_t)r * a.n_part + k] = k == 0 ? first : 0x7fffffff;
     }
 }
 

@@ -169,6 +169,13 @@ struct sr_engine {
     float rows_temp = 0.f, rows_topp = 1.f; int rows_topk = 0; unsigned rows_seed = 0, adm_count = 0;
     long long* d_adm_pick = nullptr;
     struct RowsGraph { hipGraphExec_t g = nullptr; int neos = -1, pad = 0, topk = 0; float it = 0.f, topp = 0.f; unsigned seed = 0; } rgraph[2];      // [px_mode]
+    // per-request sampling in the continuous batcher (sr_rows_per_row, sr_admit_sampling / sr_admit_stage_sampling): allocated on first use.
+    // rp_rows [MAXB] / rp_stage [MAXB]: the parameter table of the batch rows / of the staged sequences; rp_seen [n_slots][seen_words]: one
+    // repetition-penalty bitmap per KV slot; h_rp: pinned upload buffer of the staged entries
+    void* rp_mem = nullptr; RowParams *rp_rows = nullptr, *rp_stage = nullptr, *h_rp = nullptr; unsigned* rp_seen = nullptr;
+    bool rows_perrow = false;       // sr_rows_step replays the per-row graph
+    bool staged_rp = false;         // the staged admission drew its first tokens under its table entries (and marked its slots' bitmaps)
+    struct PerRowGraph { hipGraphExec_t g = nullptr; int neos = -1, pad = 0; } pgraph[2];      // [px_mode]
     hipGraphExec_t sgraph = nullptr;      // sampled decode step: bookkeeping + forward + k_sample
     int sg_B = -1, sg_neos = -1, sg_pad = 0, sg_topk = 0, sg_px = 0; float sg_it = 0.f, sg_topp = 0.f, sg_rp = 0.f; unsigned sg_seed = 0;
     int prefilled_B = 0;
@@ -803,6 +810,9 @@ int sr_engine_destroy(sr_engine* e) {
     if (e->bgraph) (void)hipGraphExecDestroy(e->bgraph);
     if (e->beam_mem) (void)hipFree(e->beam_mem);
     for (auto& r : e->rgraph) if (r.g) (void)hipGraphExecDestroy(r.g);
+    for (auto& r : e->pgraph) if (r.g) (void)hipGraphExecDestroy(r.g);
+    if (e->rp_mem) (void)hipFree(e->rp_mem);
+    if (e->h_rp) (void)hipHostFree(e->h_rp);
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     if (e->ev_copy) (void)hipEventDestroy(e->ev_copy);
     if (e->h_stage) (void)hipHostFree(e->h_stage);
@@ -1000,6 +1010,34 @@ int sr_finalize_weights(sr_engine* e, void* stream) {
     return 0;
 }
 
+// the table entry of a row admitted without parameters of its own: the shared configuration of sr_rows_sampling, keyed by the row
+static RowParams default_params(const sr_engine* e) {
+    return RowParams{e->rows_temp > 0.f ? 1.0f / e->rows_temp : 0.f, e->rows_topk, e->rows_topp, 1.0f, e->rows_seed, RP_ROW_STREAM};
+}
+
+// per-row sampling state, on first use (as the beam state: the workspace and engines that never use it are unchanged).  Every row's entry
+// starts as the shared configuration, so that rows admitted before the table existed draw exactly as they did
+static int ensure_row_params(sr_engine* e, hipStream_t s) {
+    if (e->rp_mem) return 0;
+    if (!e->h_rp) SR_TRY((int)hipHostMalloc((void**)&e->h_rp, MAXB * sizeof(RowParams)));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_rows = take(MAXB * sizeof(RowParams)), o_stage = take(MAXB * sizeof(RowParams)),
+                 o_seen = take((size_t)e->n_slots * e->seen_words * sizeof(unsigned));
+    void* m = nullptr;
+    SR_TRY((int)hipMalloc(&m, off));
+    e->rp_rows = reinterpret_cast<RowParams*>(static_cast<char*>(m) + o_rows);
+    e->rp_stage = reinterpret_cast<RowParams*>(static_cast<char*>(m) + o_stage);
+    e->rp_seen = reinterpret_cast<unsigned*>(static_cast<char*>(m) + o_seen);
+    for (int i = 0; i < MAXB; ++i) e->h_rp[i] = default_params(e);
+    hipError_t r = hipMemcpyAsync(e->rp_rows, e->h_rp, MAXB * sizeof(RowParams), hipMemcpyHostToDevice, s);
+    if (r == hipSuccess) r = hipMemsetAsync(e->rp_seen, 0, (size_t)e->n_slots * e->seen_words * sizeof(unsigned), s);
+    if (r == hipSuccess) r = hipStreamSynchronize(s);
+    if (r != hipSuccess) { (void)hipFree(m); return (int)r; }
+    e->rp_mem = m;
+    return 0;
+}
+
 // installs the staged admission's sequences into batch rows (row state + pending first token); runs on the DECODE stream, between steps
 static int commit_admission(sr_engine* e, const int32_t* rows, int n, hipStream_t s) {
     const sr_config& c = e->c;
@@ -1011,8 +1049,15 @@ static int commit_admission(sr_engine* e, const int32_t* rows, int n, hipStream_
     AdmitArgs aa{e->d_adm + off, e->d_adm + MAXB + off, e->d_adm + 2 * MAXB + off, e->d_adm + 3 * MAXB + off, e->d_adm + 4 * MAXB + off, n,
                  e->d_ctx_len, e->d_pos, e->d_slots, e->d_finished, e->d_step, e->d_row_limit, e->d_ngen,
                  e->d_amax_val, e->d_amax_idx, gemv_f32_blocks(c.t_vocab, MB, c.t_hidden, fused_norms(e, MB) ? 1 : 0), e->d_adm_slots + off};
+    if (e->staged_rp) {              // per-row table: the first tokens drawn under the staged entries, and the entries, go to the rows
+        aa.first_pick = e->d_adm_pick + off; aa.sampled = e->d_sampled;
+        aa.stage_params = e->rp_stage + off; aa.row_params = e->rp_rows;
+    } else if (e->rp_mem) {          // staged before the table existed: the shared entry, and the greedy first token where the per-row graph reads it
+        aa.row_params = e->rp_rows; aa.dflt = default_params(e);
+        if (!(e->rows_temp > 0.f)) aa.sampled = e->d_sampled;
+    }
     SR_TRY(launch_admit_rows(s, aa));
-    if (e->rows_temp > 0.f) SR_TRY(launch_scatter_rows(s, e->d_adm + off, e->d_adm_pick + off, e->d_sampled, n));   // the drawn first tokens
+    if (e->rows_temp > 0.f && !e->staged_rp) SR_TRY(launch_scatter_rows(s, e->d_adm + off, e->d_adm_pick + off, e->d_sampled, n));   // the drawn first tokens
     e->staged_n -= n;
     e->staged_off = e->staged_n ? off + n : 0;
     return 0;
@@ -1024,7 +1069,8 @@ static int commit_admission(sr_engine* e, const int32_t* rows, int n, hipStream_
 // one k_kv_fanout launch copies every prompt's prefix into the slots of its other forks.  Each staged sequence draws its own first token.
 static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* slots, int B,
                         const void* image_embeds, int n_image_rows, float* logits_out, void* stream, const int32_t* limits,
-                        float* all_logits_out = nullptr, bool commit = true, const int32_t* fanout = nullptr, const int32_t* fork_slots = nullptr) {
+                        float* all_logits_out = nullptr, bool commit = true, const int32_t* fanout = nullptr, const int32_t* fork_slots = nullptr,
+                        const sr_sampling* smp = nullptr) {
     enter(e);
     if (!e || !ids || !pos3 || !seq_lens || !slots) return fail(e, -22, "sr_prefill: null argument");
     char miss[160];
@@ -1098,6 +1144,18 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
         return fail(e, -22, "image features and image tokens do not match: %d tokens, %d feature rows", img_row, n_image_rows);
     const size_t total = reinterpret_cast<char*>(h_work + n_work) - e->h_stage;
     if (total > e->stage_bytes) return fail(e, -12, "control staging too small");
+    // once the per-row table exists, every admission stages its sequences' entries (its own, or the shared configuration restated)
+    // (h_rp is free again: stage_begin waited for the event recorded behind the previous upload, which follows this copy on its stream)
+    const bool rp_stage = limits && e->rp_mem;
+    if (rp_stage) {
+        for (int i = 0; i < n_seq; ++i) {
+            RowParams p = default_params(e);
+            if (smp) p = RowParams{smp[i].temperature > 0.f ? 1.0f / smp[i].temperature : 0.f, smp[i].top_k, smp[i].top_p, smp[i].repetition_penalty,
+                                   smp[i].seed, smp[i].stream < 0 ? RP_ROW_STREAM : (unsigned)smp[i].stream};
+            e->h_rp[i] = p;
+        }
+        SR_TRY((int)hipMemcpyAsync(e->rp_stage, e->h_rp, (size_t)n_seq * sizeof(RowParams), hipMemcpyHostToDevice, s));
+    }
     SR_TRY(stage_upload(e, 0, total, s));
     auto dmirror = [&](const void* hptr) { return e->d_stage + (reinterpret_cast<const char*>(hptr) - e->h_stage); };
     SR_TRY((int)hipMemcpyAsync(e->t_src, dmirror(h_src), (size_t)n_tok * 4, hipMemcpyDeviceToDevice, s));
@@ -1196,7 +1254,15 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
     // first token of every staged sequence: the forks of a prompt read its logits row (row map), each draws at its own staged index
     const int* row_map = n_groups ? e->d_fan : nullptr;
     SR_TRY(launch_argmax(s, e->d_logits_adm, n_seq, c.t_vocab, e->d_adm + 4 * MAXB, row_map));
-    if (e->rows_temp > 0.f) {      // sampling mode: the first token of the new rows is drawn from the admission logits
+    if (rp_stage) {                // per-row table: each staged sequence's slot bitmap = its prompt, then its first token under its own entry
+        SR_TRY(launch_mark_staged(s, e->t_src, e->t_lastrow, n_groups ? e->d_fan : nullptr, e->d_adm_slots, e->rp_seen, e->seen_words, n_seq));
+        // (salt: the shared path's seed of this admission for the entries keyed by the row -- sr_rows_sampling's draw below, restated)
+        SampleArgs sa{e->d_logits_adm, c.t_vocab, n_seq, 1.0f, 1, 1.0f, 1.0f, e->rp_seen, e->seen_words,
+                      e->rows_temp > 0.f ? 0x9E3779B9u * ++e->adm_count : 0u, nullptr, e->d_adm_pick, nullptr, 0, 0, row_map};
+        sa.params = e->rp_stage;
+        sa.seen_slot = e->d_adm_slots;
+        SR_TRY(launch_sample(s, sa));
+    } else if (e->rows_temp > 0.f) {      // sampling mode: the first token of the new rows is drawn from the admission logits
         SampleArgs sa{e->d_logits_adm, c.t_vocab, n_seq, 1.0f / e->rows_temp, e->rows_topk, e->rows_topp, 1.0f, nullptr, e->seen_words,
                       e->rows_seed ^ (0x9E3779B9u * ++e->adm_count), nullptr, e->d_adm_pick, nullptr, 0, 0, row_map};
         SR_TRY(launch_sample(s, sa));
@@ -1208,6 +1274,7 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
     }
     e->staged_n = n_seq;
     e->staged_off = 0;
+    e->staged_rp = rp_stage;
     if (commit) return commit_admission(e, fork_slots ? fork_slots : slots, n_seq, s);
     return 0;
 }
@@ -1247,6 +1314,35 @@ int sr_rows_begin(sr_engine* e, void* stream) {
     e->prefilled_B = e->c.max_batch;
     e->h_ctx_hi = 0;
     e->rows_temp = 0.f;
+    e->rows_perrow = e->staged_rp = false;
+    return 0;
+}
+
+int sr_rows_per_row(sr_engine* e, int on, void* stream) {
+    enter(e);
+    if (!e || !e->rows_mode) return fail(e, -22, "sr_rows_per_row: call sr_rows_begin first");
+    hipStream_t s = (hipStream_t)stream;
+    if (!on) { e->rows_perrow = false; return 0; }
+    SR_TRY(ensure_row_params(e, s));
+    if (!e->rows_perrow && !(e->rows_temp > 0.f)) {
+        // greedy rows keep their pending token in the LM-head partials (k_step reduces them); the per-row graph reads d_sampled
+        const int MB = e->c.max_batch;
+        SR_TRY(launch_next_ids(s, e->d_amax_val, e->d_amax_idx, gemv_f32_blocks(e->c.t_vocab, MB, e->c.t_hidden, fused_norms(e, MB) ? 1 : 0), MB,
+                               e->d_sampled));
+    }
+    e->rows_perrow = true;
+    return 0;
+}
+
+// refuses a bad entry by name; -> 0 or the error code
+static int check_sampling(sr_engine* e, const char* fn, const sr_sampling* p, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (!(p[i].temperature >= 0.f)) return fail(e, -22, "%s: sequence %d: temperature %g < 0", fn, i, (double)p[i].temperature);
+        if (p[i].top_k > 1024) return fail(e, -22, "%s: sequence %d: top_k %d > 1024", fn, i, p[i].top_k);
+        if (!(p[i].top_p > 0.f && p[i].top_p <= 1.f)) return fail(e, -22, "%s: sequence %d: top_p %g outside (0, 1]", fn, i, (double)p[i].top_p);
+        if (!(p[i].repetition_penalty > 0.f))
+            return fail(e, -22, "%s: sequence %d: repetition_penalty %g <= 0", fn, i, (double)p[i].repetition_penalty);
+    }
     return 0;
 }
 
@@ -1325,6 +1421,36 @@ int sr_admit_stage_fanout(sr_engine* e, const int64_t* ids, const int64_t* pos3,
 int sr_admit_stage(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* kv_slots, const int32_t* max_new,
                    int n, const void* image_embeds, int n_image_rows, float* logits_out, void* stream) {
     return sr_admit_stage_fanout(e, ids, pos3, seq_lens, nullptr, kv_slots, max_new, n, image_embeds, n_image_rows, logits_out, stream);
+}
+
+int sr_admit_stage_sampling(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* fanout,
+                            const int32_t* kv_slots, const int32_t* max_new, const sr_sampling* sampling, int n, const void* image_embeds,
+                            int n_image_rows, float* logits_out, void* stream) {
+    enter(e);
+    if (!e || !kv_slots || !max_new || !seq_lens || !sampling) return fail(e, -22, "sr_admit_stage_sampling: null argument");
+    const int total = check_fanout(e, "sr_admit_stage_sampling", seq_lens, fanout, kv_slots, n, e->n_slots, "KV slot", max_new);
+    if (total < 0) return total;
+    if (int rc = check_sampling(e, "sr_admit_stage_sampling", sampling, total)) return rc;
+    SR_TRY(ensure_row_params(e, (hipStream_t)stream));
+    int32_t first[MAXB];
+    first_forks(fanout, kv_slots, n, first);
+    return prefill_impl(e, ids, pos3, seq_lens, first, n, image_embeds, n_image_rows, logits_out, stream, max_new, nullptr, false, fanout, kv_slots,
+                        sampling);
+}
+
+int sr_admit_sampling(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* fanout, const int32_t* rows,
+                      const int32_t* max_new, const sr_sampling* sampling, int n, const void* image_embeds, int n_image_rows, float* logits_out,
+                      void* stream) {
+    enter(e);
+    if (!e || !rows || !max_new || !seq_lens || !sampling) return fail(e, -22, "sr_admit_sampling: null argument");
+    const int total = check_fanout(e, "sr_admit_sampling", seq_lens, fanout, rows, n, e->c.max_batch, "row", max_new);
+    if (total < 0) return total;
+    if (int rc = check_sampling(e, "sr_admit_sampling", sampling, total)) return rc;
+    SR_TRY(ensure_row_params(e, (hipStream_t)stream));
+    int32_t first[MAXB];
+    first_forks(fanout, rows, n, first);
+    return prefill_impl(e, ids, pos3, seq_lens, first, n, image_embeds, n_image_rows, logits_out, stream, max_new, nullptr, true, fanout, rows,
+                        sampling);
 }
 
 int sr_admit_commit(sr_engine* e, const int32_t* rows, int n, void* stream) {
@@ -1682,6 +1808,33 @@ int sr_rows_step(sr_engine* e, int n_steps, const int32_t* host_eos, int n_eos, 
     hipStream_t s = (hipStream_t)stream;
     if (n_eos) SR_TRY((int)hipMemcpyAsync(e->d_eos, host_eos, n_eos * 4, hipMemcpyHostToDevice, s));
     const int B = e->c.max_batch;
+    if (e->rows_perrow) {          // per-row step: mark the consumed tokens, consume them, forward, draw every row under its own table entry
+        const sr_config& c = e->c;
+        auto& pg = e->pgraph[e->px_mode];
+        if (pg.g == nullptr || pg.neos != n_eos || pg.pad != pad_id) {
+            if (pg.g) { (void)hipGraphExecDestroy(pg.g); pg.g = nullptr; }
+            const int hn = fused_norms(e, B) ? 1 : 0;
+            SampleArgs sa{e->d_logits, c.t_vocab, B, 1.0f, 1, 1.0f, 1.0f, e->rp_seen, e->seen_words, 0u, e->d_step, e->d_sampled,
+                          e->d_amax_val, gemv_f32_blocks(c.t_vocab, B, c.t_hidden, hn), gemv_f32_block_rows(c.t_vocab, B, c.t_hidden, hn)};
+            sa.params = e->rp_rows;
+            sa.seen_slot = e->d_slots;
+            hipGraph_t g = nullptr;
+            SR_TRY((int)hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
+            int rc = launch_mark_rows(e->cap_stream, e->d_sampled, e->d_finished, e->d_slots, e->rp_seen, e->seen_words, B);
+            if (!rc) rc = enqueue_step(e, B, n_eos, pad_id, nullptr, e->cap_stream, e->d_sampled);
+            if (!rc) rc = enqueue_decode_forward(e, B, e->cap_stream);
+            if (!rc) rc = launch_sample(e->cap_stream, sa);
+            hipError_t er = hipStreamEndCapture(e->cap_stream, &g);
+            if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+            SR_TRY((int)er);
+            er = hipGraphInstantiate(&pg.g, g, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(g);
+            SR_TRY((int)er);
+            pg.neos = n_eos; pg.pad = pad_id;
+        }
+        for (int i = 0; i < n_steps; ++i) SR_TRY((int)hipGraphLaunch(pg.g, s));
+        return 0;
+    }
     if (e->rows_temp > 0.f) {      // sampled step: consume the drawn tokens, forward, draw the next ones for every row
         const sr_config& c = e->c;
         const float it = 1.0f / e->rows_temp;

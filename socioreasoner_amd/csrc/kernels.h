@@ -213,12 +213,22 @@ struct StepArgs {
 // q = fp8(W / scale) -> W8 (tiled8); W itself is overwritten with q as bf16 (what the prefill GEMM multiplies, scaled in its epilogue)
 int launch_quant_f8(hipStream_t s, bf16_t* W_tiled, int N, int K, unsigned char* W8, float* scale);
 int launch_step(hipStream_t s, const StepArgs& a);
+// one row's sampling parameters.  inv_temp 0 = greedy (run as top_k = 1: the lowest id among the maxima of the penalised logits); top_k <= 0 or
+// >= V = no top-k bound (k_sample_full).  The draw for step s uses the key (seed, stream, s); stream RP_ROW_STREAM = the draw's own index b
+// (the shared path's key: the row in a decode step, the staged index at admission, where SampleArgs::seed salts it as sr_rows_sampling does)
+struct RowParams { float inv_temp; int top_k; float top_p; float rep_penalty; unsigned seed; unsigned stream; };
+constexpr unsigned RP_ROW_STREAM = 0xffffffffu;
 // continuous batching: install n freshly prefilled sequences into batch rows (state + pending first token)
 struct AdmitArgs {
     const int* rows; const int* ctx; const int* pos; const int* limit; const int* first_tok; int n;
     int* ctx_len; int* d_pos; int* slots; int* finished; int* step; int* row_limit; int* n_gen;
     float* amax_val; int* amax_idx; int n_part;
     const int* kv_slot;         // KV-cache slot of each admitted sequence (null: slot = row)
+    // per-row sampling (optional): the staged sequences' drawn first tokens (then fed through the partials AND sampled[row]; sampled without
+    // first_pick: sampled[row] = first_tok) and their parameter entries, copied to row_params[row]
+    const long long* first_pick = nullptr; long long* sampled = nullptr;
+    const RowParams* stage_params = nullptr; RowParams* row_params = nullptr;
+    RowParams dflt{};           // row_params without stage_params: the entry every admitted row gets (the shared configuration, restated)
 };
 int launch_admit_rows(hipStream_t s, const AdmitArgs& a);
 // ------------------------------------------------------------------ kvfork.hip
@@ -270,8 +280,17 @@ struct SampleArgs {
     long long* out;                         // [B] chosen token
     const float* blk_max; int n_blk, blk_rows;   // optional: the LM head's per-block maxima [B][n_blk], block j = ids [j*blk_rows, (j+1)*blk_rows)
     const int* row_map = nullptr;           // optional: draw b reads logits (and blk_max) row row_map[b]; its RNG stream stays (seed, b, step[b])
+    // optional per-row parameter table [B] (continuous batching with per-request sampling): when given it replaces inv_temp, top_k, top_p,
+    // rep_penalty and the RNG key of every draw; `seed` is then XORed into the seed of the entries whose stream is RP_ROW_STREAM only
+    const RowParams* params = nullptr;
+    const int* seen_slot = nullptr;         // optional: draw b's bitmap row is seen_slot[b] (the row's KV slot) instead of b
 };
 int launch_sample(hipStream_t s, const SampleArgs& a);
+// marks every unfinished row's pending token (chosen[b]) in the bitmap of its KV slot; B <= 128 (continuous batching, inside the captured step)
+int launch_mark_rows(hipStream_t s, const long long* chosen, const int* finished, const int* slots, unsigned* seen, int seen_words, int B);
+// staged admission: sequence i's bitmap (KV slot slots[i]) is cleared and marked with the tokens of its prompt map[i] (t_src rows
+// lastrow[p - 1] + 1 .. lastrow[p]); map null: prompt i.  One block per staged sequence
+int launch_mark_staged(hipStream_t s, const int* src, const int* lastrow, const int* map, const int* slots, unsigned* seen, int seen_words, int n);
 int launch_scatter_rows(hipStream_t s, const int* rows, const long long* src, long long* dst, int n);   // dst[rows[i]] = src[i]
 int launch_mark_prompt(hipStream_t s, const int* src, const int* lastrow, unsigned* seen, int seen_words, int B);
 int launch_mark_chosen(hipStream_t s, const long long* chosen, unsigned* seen, int seen_words, int B);

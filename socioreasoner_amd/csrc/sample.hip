@@ -61,6 +61,32 @@ __device__ int find_bin(const int* hist, int nb, int need, int* above, int* s_tm
     return s_tmp[0];
 }
 
+// the parameters of draw b: SampleArgs' scalars, or its entry of the per-row table (greedy = top_k 1 at temperature 1, top_p 1)
+struct RowDraw { float inv_temp, top_p, rp; int top_k; bool full; unsigned seed, stream; const unsigned* seen; };
+__device__ __forceinline__ RowDraw row_draw(const SampleArgs& a, int b) {
+    RowDraw d{a.inv_temp, a.top_p, a.rep_penalty, a.top_k, false, a.seed, (unsigned)b, nullptr};
+    if (a.params) {
+        const RowParams p = a.params[b];
+        const bool greedy = !(p.inv_temp > 0.f);
+        d.inv_temp = greedy ? 1.f : p.inv_temp;
+        d.top_p = greedy ? 1.f : p.top_p;
+        d.top_k = greedy ? 1 : p.top_k;
+        d.full = !greedy && (p.top_k <= 0 || p.top_k >= a.V);
+        d.rp = p.rep_penalty;
+        if (p.stream == RP_ROW_STREAM) d.seed = p.seed ^ a.seed;      // the shared path's key, restated
+        else { d.seed = p.seed; d.stream = p.stream; }
+    }
+    // (rp == 1 changes no value: no bitmap, so that the LM head's block maxima stay usable as they are)
+    if (a.seen && d.rp != 1.0f) d.seen = a.seen + (size_t)(a.seen_slot ? a.seen_slot[b] : b) * a.seen_words;
+    return d;
+}
+// the uniform of draw b: counter-based, key (seed, stream, step[b]) -- step 0 at admission (no step array), the row's step counter afterwards
+__device__ __forceinline__ float draw_u(const SampleArgs& a, const RowDraw& d, int b) {
+    const int stp = a.step ? a.step[b] : 0;
+    const uint32_t h = hmix(d.seed ^ hmix(d.stream * 0x9E3779B1u + (uint32_t)stp * 0x85EBCA77u + 0x1234567u));
+    return (float)(h >> 8) * (1.0f / 16777216.0f);
+}
+
 __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     __shared__ int hist[4096];
     __shared__ unsigned long long cand[KMAX];      // (sortable value << 32) | (0xffffffff - id): descending order = value desc, id asc
@@ -71,18 +97,26 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = a.row_map ? a.row_map[b] : b;         // logits row (forks of one prompt share it); b keeps the RNG stream
     const float* row = a.logits + (size_t)lr * a.V;
-    const unsigned* seen = a.seen ? a.seen + (size_t)b * a.seen_words : nullptr;
-    const int K = a.top_k;
+    const RowDraw P = row_draw(a, b);
+    if (P.full) return;                                  // (per-row table: a row without a top-k bound is k_sample_full's)
+    const unsigned* seen = P.seen;
+    const int K = P.top_k;
     // ---- candidate reduction through the LM head's per-block maxima (exact): an element of the global top-K is >= the K-th
     // largest element, which is >= the K-th largest BLOCK maximum, so it lives in one of the blocks whose maximum reaches
     // that value.  With K = 100 that leaves ~100 x 64 of the 151 936 logits to look at.  Not usable with a repetition
-    // penalty (it changes the values the maxima were taken from) or when ties make the block set too large.
+    // penalty below 1 or when ties make the block set too large.
+    // With a repetition penalty rp >= 1 (pen(l) = l > 0 ? l / rp : l * rp on the tokens already seen) the penalised value of a token is <= its raw
+    // logit, and pen is monotone.  Block j therefore holds a penalised value >= pen(m_j) (its maximum, penalised or not), so the K blocks with the
+    // largest maxima give K values >= pen(M_K), M_K = the K-th largest block maximum: the K-th largest PENALISED value is >= pen(M_K).  A token of
+    // the penalised top-K has a penalised value >= pen(M_K), hence a raw logit >= pen(M_K), hence lives in a block with m_j >= pen(M_K).  The
+    // threshold drops from M_K to pen(M_K): the same select on the block maxima, then every block whose maximum reaches pen(M_K) (ties at the
+    // K-th value included: they are >= pen(M_K) too, and the tie pass below scans the whole row anyway).  rp < 1 raises values: full scan.
     __shared__ int sel_blk[KMAX];
     __shared__ int s_nsel;
     int n_items = a.V;                      // number of candidate positions; position -> token id through id_of
     const int R = a.blk_rows;
     bool filtered = false;
-    if (a.blk_max && !seen && a.n_blk > K && R > 0) {
+    if (a.blk_max && (!seen || P.rp >= 1.0f) && a.n_blk > K && R > 0) {
         const float* bm = a.blk_max + (size_t)lr * a.n_blk;
         uint32_t pfx = 0;
         int need_b = K;
@@ -103,6 +137,10 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
             pfx |= (uint32_t)bin << sh;
             __syncthreads();
         }
+        if (seen) {                                        // pen(M_K): the bound on the penalised K-th value (see above)
+            const float mk = unkey(pfx);
+            pfx = fkey(mk > 0.f ? mk / P.rp : mk * P.rp);
+        }
         if (tid == 0) s_nsel = 0;
         __syncthreads();
         for (int i = tid; i < a.n_blk; i += NT)
@@ -121,7 +159,7 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     auto adj = [&](int id) -> float {
         if (id >= a.V) return -INFINITY;
         float l = row[id];
-        if (seen && ((seen[id >> 5] >> (id & 31)) & 1u)) l = l > 0.f ? l / a.rep_penalty : l * a.rep_penalty;
+        if (seen && ((seen[id >> 5] >> (id & 31)) & 1u)) l = l > 0.f ? l / P.rp : l * P.rp;
         return l;
     };
     // ---- radix select of the K-th largest key
@@ -205,7 +243,7 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     // ---- softmax with temperature over the K candidates
     const float vmax = unkey((uint32_t)(cand[0] >> 32));
     float e = 0.f;
-    if (tid < K) e = __expf((unkey((uint32_t)(cand[tid] >> 32)) - vmax) * a.inv_temp);
+    if (tid < K) e = __expf((unkey((uint32_t)(cand[tid] >> 32)) - vmax) * P.inv_temp);
     float ssum = wave_sum(e);
     if (lane == 0) s_red[wave] = ssum;
     __syncthreads();
@@ -230,13 +268,11 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     // ---- top-p: keep j while the tail mass 1 - c_{j-1} exceeds 1 - top_p, i.e. c_{j-1} < top_p (j = 0 always)
     if (tid == 0) { s_tmp[0] = 1; s_tmp[1] = 0; }
     __syncthreads();
-    if (tid >= 1 && tid < K && prob[tid - 1] < a.top_p) atomicMax(&s_tmp[0], tid + 1);      // prefix property: max index + 1 = count
+    if (tid >= 1 && tid < K && prob[tid - 1] < P.top_p) atomicMax(&s_tmp[0], tid + 1);      // prefix property: max index + 1 = count
     __syncthreads();
     const int n_keep = s_tmp[0];
     const float mass = prob[n_keep - 1];
-    const int stp = a.step ? a.step[b] : 0;
-    const uint32_t h = hmix(a.seed ^ hmix((uint32_t)b * 0x9E3779B1u + (uint32_t)stp * 0x85EBCA77u + 0x1234567u));
-    const float u = (float)(h >> 8) * (1.0f / 16777216.0f);
+    const float u = draw_u(a, P, b);
     const float target = u * mass;
     if (tid < n_keep && prob[tid] <= target) atomicAdd(&s_tmp[1], 1);                       // number of c_j <= target
     __syncthreads();
@@ -292,10 +328,13 @@ __global__ __launch_bounds__(NT) void k_sample_full(SampleArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = a.row_map ? a.row_map[b] : b;         // logits row (forks of one prompt share it); b keeps the RNG stream
     const float* row = a.logits + (size_t)lr * a.V;
-    const unsigned* seen = a.seen ? a.seen + (size_t)b * a.seen_words : nullptr;
+    const RowDraw P = row_draw(a, b);
+    if (a.params && !P.full) return;                     // (per-row table: rows with a top-k bound and greedy rows are k_sample's)
+    const unsigned* seen = P.seen;
+    const float inv_temp = P.inv_temp;
     auto adj = [&](int id) -> float {
         float l = row[id];
-        if (seen && ((seen[id >> 5] >> (id & 31)) & 1u)) l = l > 0.f ? l / a.rep_penalty : l * a.rep_penalty;
+        if (seen && ((seen[id >> 5] >> (id & 31)) & 1u)) l = l > 0.f ? l / P.rp : l * P.rp;
         return l;
     };
     // ---- max and partition function (fixed-order block reductions)
@@ -308,15 +347,15 @@ __global__ __launch_bounds__(NT) void k_sample_full(SampleArgs a) {
     for (int w = 1; w < NT / 64; ++w) mx = fmaxf(mx, s_red[w]);
     __syncthreads();
     float z = 0.f;
-    for (int i = tid; i < a.V; i += NT) z += __expf((adj(i) - mx) * a.inv_temp);
+    for (int i = tid; i < a.V; i += NT) z += __expf((adj(i) - mx) * inv_temp);
     z = wave_sum(z);
     if (lane == 0) s_red[wave] = z;
     __syncthreads();
     float Z = 0.f;
     for (int w = 0; w < NT / 64; ++w) Z += s_red[w];
     const float inv_z = 1.0f / Z;
-    auto prob_fx = [&](float l) -> unsigned long long { return (unsigned long long)(__expf((l - mx) * a.inv_temp) * inv_z * (float)(1ull << FX_SHIFT)); };
-    const unsigned long long want = a.top_p >= 1.0f ? ~0ull : (unsigned long long)((double)a.top_p * (double)(1ull << FX_SHIFT));
+    auto prob_fx = [&](float l) -> unsigned long long { return (unsigned long long)(__expf((l - mx) * inv_temp) * inv_z * (float)(1ull << FX_SHIFT)); };
+    const unsigned long long want = P.top_p >= 1.0f ? ~0ull : (unsigned long long)((double)P.top_p * (double)(1ull << FX_SHIFT));
     // ---- radix descent on mass: tau = the smallest key whose strictly-above mass is < top_p
     uint32_t prefix = 0;
     unsigned long long above = 0;                   // mass of the keys above the current prefix range
@@ -382,13 +421,11 @@ __global__ __launch_bounds__(NT) void k_sample_full(SampleArgs a) {
         const float l = adj(i);
         const uint32_t k = fkey(l);
         const bool keep = k > tau || (k == tau && seen_ties++ < r_keep);
-        if (keep) msum += __expf((l - mx) * a.inv_temp) * inv_z;
+        if (keep) msum += __expf((l - mx) * inv_temp) * inv_z;
     }
     float total;
     const float before = block_excl_scan(tid, msum, s_scan, total);          // fixed association: lanes inside a wave, then the waves in order -> run-to-run identical
-    const int stp = a.step ? a.step[b] : 0;
-    const uint32_t h = hmix(a.seed ^ hmix((uint32_t)b * 0x9E3779B1u + (uint32_t)stp * 0x85EBCA77u + 0x1234567u));
-    const float u = (float)(h >> 8) * (1.0f / 16777216.0f);
+    const float u = draw_u(a, P, b);
     const float target = u * total;
     if (tid == 0) s_i[1] = -1;
     __syncthreads();
@@ -409,7 +446,7 @@ __global__ __launch_bounds__(NT) void k_sample_full(SampleArgs a) {
             const bool keep = k > tau || (k == tau && st++ < r_keep);
             if (!keep) continue;
             lastk = i;
-            run += __expf((l - mx) * a.inv_temp) * inv_z;
+            run += __expf((l - mx) * inv_temp) * inv_z;
             if (target < run) { pick = i; break; }
         }
         a.out[b] = (long long)(pick >= 0 ? pick : lastk);
@@ -436,6 +473,28 @@ __global__ void k_mark_chosen(const long long* chosen, unsigned* seen, int seen_
     }
 }
 
+// continuous batching: the token each unfinished row consumes in this step goes into its KV slot's bitmap (finished / aborted rows mark nothing)
+__global__ void k_mark_rows(const long long* chosen, const int* finished, const int* slots, unsigned* seen, int seen_words, int B) {
+    const int b = threadIdx.x;
+    if (b < B && !finished[b]) {
+        const long long id = chosen[b];
+        atomicOr(&seen[(size_t)slots[b] * seen_words + (id >> 5)], 1u << (id & 31));
+    }
+}
+// staged admission: a fresh bitmap per staged sequence (its KV slot may have served another request), marked with its prompt's tokens
+// (the forks of a prompt each get a copy: the prompt is re-marked into every fork's slot)
+__global__ void k_mark_staged(const int* src, const int* lastrow, const int* map, const int* slots, unsigned* seen, int seen_words) {
+    const int i = blockIdx.x, p = map ? map[i] : i;
+    const int t0 = p == 0 ? 0 : lastrow[p - 1] + 1, t1 = lastrow[p] + 1;
+    unsigned* row = seen + (size_t)slots[i] * seen_words;
+    for (int w = threadIdx.x; w < seen_words; w += blockDim.x) row[w] = 0u;
+    __syncthreads();
+    for (int t = t0 + threadIdx.x; t < t1; t += blockDim.x) {
+        const int id = src[t];
+        if (id >= 0) atomicOr(&row[id >> 5], 1u << (id & 31));
+    }
+}
+
 __global__ void k_scatter_rows(const int* rows, const long long* src, long long* dst, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[rows[i]] = src[i];
@@ -451,6 +510,13 @@ int launch_scatter_rows(hipStream_t s, const int* rows, const long long* src, lo
 }
 int launch_sample(hipStream_t s, const SampleArgs& a) {
     if (a.B <= 0) return 0;
+    if (a.params) {                                  // per-row table: one k_sample launch (top-k and greedy rows) + one k_sample_full (unbounded rows)
+        hipLaunchKernelGGL(k_sample, dim3(a.B), dim3(NT), 0, s, a);
+        SR_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_sample_full, dim3(a.B), dim3(NT), 0, s, a);
+        SR_CHECK_LAUNCH();
+        return 0;
+    }
     if (!(a.inv_temp > 0.f) || !(a.top_p > 0.f)) return -22;
     if (a.top_k <= 0 || a.top_k >= a.V) {            // no top-k bound (vLLM's -1): nucleus sampling over the whole vocabulary
         hipLaunchKernelGGL(k_sample_full, dim3(a.B), dim3(NT), 0, s, a);
@@ -464,6 +530,19 @@ int launch_sample(hipStream_t s, const SampleArgs& a) {
 }
 int launch_mark_prompt(hipStream_t s, const int* src, const int* lastrow, unsigned* seen, int seen_words, int B) {
     hipLaunchKernelGGL(k_mark_prompt, dim3(B), dim3(256), 0, s, src, lastrow, seen, seen_words);
+    SR_CHECK_LAUNCH();
+    return 0;
+}
+int launch_mark_rows(hipStream_t s, const long long* chosen, const int* finished, const int* slots, unsigned* seen, int seen_words, int B) {
+    if (B <= 0) return 0;
+    if (B > 128) return -22;
+    hipLaunchKernelGGL(k_mark_rows, dim3(1), dim3(128), 0, s, chosen, finished, slots, seen, seen_words, B);
+    SR_CHECK_LAUNCH();
+    return 0;
+}
+int launch_mark_staged(hipStream_t s, const int* src, const int* lastrow, const int* map, const int* slots, unsigned* seen, int seen_words, int n) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(k_mark_staged, dim3(n), dim3(256), 0, s, src, lastrow, map, slots, seen, seen_words);
     SR_CHECK_LAUNCH();
     return 0;
 }

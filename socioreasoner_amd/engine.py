@@ -275,11 +275,21 @@ class Engine:
         """After rows_begin: all rows sample (k_sample) instead of taking the arg-max; temperature 0 = greedy again."""
         L.check(self.lib.sr_rows_sampling(self._h, C.c_float(temperature), int(top_k), C.c_float(top_p), int(seed) & 0xffffffff), self._h, "sr_rows_sampling")
 
+    def rows_per_row(self, on: bool):
+        """After rows_begin: the next rows_step calls replay the per-row step (every row draws under its own table entry, sr_rows_per_row) or,
+        on=False, the shared greedy / sampled step again.  The first call allocates the per-row state."""
+        L.check(self.lib.sr_rows_per_row(self._h, 1 if on else 0, self._s()), self._h, "sr_rows_per_row")
+
     def admit(self, rows: Sequence[int], ids: Sequence[np.ndarray], pos3: Sequence[np.ndarray], max_new: Sequence[int],
-              image_embeds: torch.Tensor | None = None, return_logits: bool = False, fanout: Sequence[int] | None = None):
+              image_embeds: torch.Tensor | None = None, return_logits: bool = False, fanout: Sequence[int] | None = None,
+              sampling: Sequence[tuple] | None = None):
         """Prefill sequences into free batch rows without disturbing running ones; row i stops after max_new[i] tokens.
         fanout: prompt i becomes fanout[i] sequences (prefilled once, its KV prefix copied on the device); `rows` then holds one row per
-        sequence, prompt-major, and max_new stays per prompt.  The logits (return_logits) have one row per prompt."""
+        sequence, prompt-major, and max_new stays per prompt.  The logits (return_logits) have one row per prompt.
+        sampling: one (temperature, top_k, top_p, repetition_penalty, seed, stream) per SEQUENCE (sr_admit_sampling; temperature 0 = greedy,
+        stream < 0 = the row's stream of rows_sampling)."""
+        if sampling is not None:
+            return self._admit_sampling(False, rows, ids, pos3, max_new, image_embeds, return_logits, fanout, sampling)
         n = len(ids)
         lens = np.array([len(x) for x in ids], dtype=np.int32)
         flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
@@ -304,11 +314,41 @@ class Engine:
                                              lg_p, self._s()), self._h, "sr_admit_fanout")
         return logits
 
+    _SMP = np.dtype([("temperature", "<f4"), ("top_k", "<i4"), ("top_p", "<f4"), ("repetition_penalty", "<f4"), ("seed", "<u4"), ("stream", "<i4")])
+
+    def _admit_sampling(self, stage, dst, ids, pos3, max_new, image_embeds, return_logits, fanout, sampling):
+        """admit / admit_stage with one sr_sampling entry per sequence (sr_admit_sampling / sr_admit_stage_sampling)"""
+        n = len(ids)
+        lens = np.array([len(x) for x in ids], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
+        p3 = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int64).reshape(3, -1) for p in pos3], axis=1))
+        d = np.asarray(list(dst), dtype=np.int32)
+        mn = np.asarray(list(max_new), dtype=np.int32)
+        fo = None if fanout is None else np.asarray(list(fanout), dtype=np.int32)
+        assert len(d) == (n if fo is None else int(fo.sum())), "one row / KV slot per sequence"
+        smp = np.array([(float(t), int(k), float(p), float(rp), int(s) & 0xffffffff, int(st)) for t, k, p, rp, s, st in sampling], dtype=self._SMP)
+        assert len(smp) == len(d), "one sampling entry per sequence"
+        n_img = 0 if image_embeds is None else int(image_embeds.shape[0])
+        if image_embeds is not None:
+            image_embeds = image_embeds.contiguous()
+            assert image_embeds.dtype == torch.bfloat16
+        logits = torch.empty(n, self.geom.text.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
+        fn = self.lib.sr_admit_stage_sampling if stage else self.lib.sr_admit_sampling
+        L.check(fn(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
+                   fo.ctypes.data_as(L._i32p) if fo is not None else None, d.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p),
+                   C.c_void_p(smp.ctypes.data), n, C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None, n_img,
+                   C.c_void_p(logits.data_ptr()) if logits is not None else None, self._s()),
+                self._h, "sr_admit_stage_sampling" if stage else "sr_admit_sampling")
+        return logits
+
     def admit_stage(self, kv_slots: Sequence[int], ids: Sequence[np.ndarray], pos3: Sequence[np.ndarray], max_new: Sequence[int],
-                    image_embeds: torch.Tensor | None = None, fanout: Sequence[int] | None = None, return_logits: bool = False):
+                    image_embeds: torch.Tensor | None = None, fanout: Sequence[int] | None = None, return_logits: bool = False,
+                    sampling: Sequence[tuple] | None = None):
         """First half of an admission, on the CURRENT torch stream (normally a CU-masked side stream): prefill into spare KV slots, LM
         head, first token.  No row state is touched; admit_commit installs the sequences into rows later.  fanout: as admit (kv_slots then
-        has one slot per forked sequence, prompt-major)."""
+        has one slot per forked sequence, prompt-major); sampling: as admit."""
+        if sampling is not None:
+            return self._admit_sampling(True, kv_slots, ids, pos3, max_new, image_embeds, return_logits, fanout, sampling)
         n = len(ids)
         lens = np.array([len(x) for x in ids], dtype=np.int32)
         flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))

@@ -110,6 +110,9 @@ SIGNATURES = {
     "sr_op_kv_suffix_copy": (C.c_int, [_vp, _vp, _i, C.c_int64, _i, _i, _vp, _i, _i, _vp]),
     "sr_op_beam_select": (C.c_int, [_vp, _i, _i, _i, _i32p, _i, _i, _i, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_switches_reload": (C.c_int, []),
+    "sr_admit_sampling": (C.c_int, [_vp, _i64p, _i64p, _i32p, _i32p, _i32p, _i32p, _vp, _i, _vp, _i, _vp, _vp]),
+    "sr_admit_stage_sampling": (C.c_int, [_vp, _i64p, _i64p, _i32p, _i32p, _i32p, _i32p, _vp, _i, _vp, _i, _vp, _vp]),
+    "sr_rows_per_row": (C.c_int, [_vp, _i, _vp]),
 }
 
 

@@ -35,6 +35,21 @@ def foreign_gpu_load(begin: bool) -> None:
     _FOREIGN["epoch"] += 1
 
 
+def _config(s: Optional[dict]) -> tuple:
+    """(temperature, top_k, top_p) of a sampling dict as the engine draws it: (0.0, 1, 1.0) = greedy (None, temperature <= 1e-5 or top_k 1)"""
+    if not s:
+        return (0.0, 1, 1.0)
+    t = float(s.get("temperature", 1.0) if s.get("temperature") is not None else 1.0)
+    k = -1 if s.get("top_k") is None else int(s["top_k"])
+    if t <= 1e-5 or k == 1:
+        return (0.0, 1, 1.0)
+    return (t, k, float(s.get("top_p", 1.0) or 1.0))
+
+
+def _penalty(s: dict) -> float:
+    return 1.0 if s.get("repetition_penalty") is None else float(s["repetition_penalty"])
+
+
 @dataclass
 class Request:
     ids: np.ndarray                       # int64 [S], image placeholders already expanded
@@ -45,12 +60,19 @@ class Request:
     tag: object = None
     aborted: bool = False                 # set by the serving loop: the row runs to its end, its result is discarded
     n: int = 1                            # sequences sampled from this prompt (forks of one admission); n > 1: reported with n token lists
+    # this request's own {"temperature", "top_k", "top_p", "repetition_penalty", "seed"} (absent keys: 1.0 / -1 / 1.0 / 1.0 / none); None = the
+    # batcher's configuration.  temperature <= 1e-5 or top_k == 1: greedy (the arg-max of the penalised logits).  With a seed its forks draw
+    # from the streams (seed, fork): tokens that depend on no row, slot or neighbour; without one the batcher picks a seed of its own per request
+    sampling: Optional[dict] = None
 
 
 class ContinuousBatcher:
     def __init__(self, engine, eos: Sequence[int], pad_id: int, steps_per_poll: int = 8, sampling: Optional[dict] = None,
-                 time_phases: bool = False, overlap: bool = False, admit_cus_per_se="auto"):
-        """sampling: None = greedy, else {"temperature", "top_k" (1..1024), "top_p", "seed"} shared by all requests.
+                 time_phases: bool = False, overlap: bool = False, admit_cus_per_se="auto", per_row: Optional[bool] = None):
+        """sampling: None = greedy, else {"temperature", "top_k" (1..1024), "top_p", "seed"} shared by all requests that bring no
+        Request.sampling of their own.  Requests with their own parameters run in the same rows, drawn by the per-row step (sr_rows_per_row);
+        per_row: None = that step only while some running row has parameters of its own (otherwise the shared greedy / sampled step), True =
+        always (a uniform table gives the shared step's tokens).
         time_phases: bracket every ViT / prefill / decode call with events on the launch stream (phase_ms() sums them).
         overlap: admissions are STAGED into spare KV slots (engine.kv_slots > max_batch) on a CU-masked side stream while the running
         rows keep decoding on the rest of the chip, and committed into rows as they free up (socioreasoner_amd/streams.py).
@@ -103,10 +125,56 @@ class ContinuousBatcher:
         self.pending: deque = deque()
         # rounds / host_ms / poll_wait_ms (round 5): scheduling rounds, host time spent in them OUTSIDE the poll's wait for the device, and that wait --
         # with N ranks on one node a flat 1 -> N curve shows here as host_ms per round growing with N (host contention) rather than poll_wait_ms
-        self.stats = {"admitted": 0, "admitted_prompts": 0, "steps": 0, "admissions": 0, "staged_shared": 0, "steps_shared": 0, "shares": [], "rounds": 0, "host_ms": 0.0, "poll_wait_ms": 0.0}
+        self.stats = {"admitted": 0, "admitted_prompts": 0, "steps": 0, "admissions": 0, "staged_shared": 0, "steps_shared": 0, "shares": [], "rounds": 0, "host_ms": 0.0, "poll_wait_ms": 0.0,
+                      "steps_per_row": 0}
+        self._default = _config(sampling)          # the shared configuration: (temperature (0 = greedy), top_k, top_p)
+        self._seed = int(sampling.get("seed", 0) or 0) if sampling else 0
+        self._serial = 0                            # requests given a seed of their own so far
+        self.row_own: Dict[int, bool] = {}          # row -> it runs under parameters of its own
+        self._force_per_row = bool(per_row)
+        self._per_row = False
         engine.rows_begin()
         if sampling:
             engine.rows_sampling(float(sampling["temperature"]), int(sampling["top_k"]), float(sampling.get("top_p", 1.0)), int(sampling.get("seed", 0)))
+        if self._force_per_row:
+            self._sync_mode()
+
+    # ------------------------------------------------------------------ per-request sampling parameters
+    def _own(self, r: Request) -> bool:
+        """does r run under parameters of its own?  (a dict equal to the batcher's configuration, without penalty or seed, does not)"""
+        s = r.sampling
+        if s is None:
+            return False
+        return _penalty(s) != 1.0 or s.get("seed") is not None or _config(s) != self._default
+
+    def _entries(self, r: Request) -> list:
+        """the engine's entries (temperature, top_k, top_p, repetition_penalty, seed, stream) of r's forks: the batcher's configuration on the
+        rows' streams, or r's own parameters on the streams (seed, fork) -- its own seed, or one the batcher derives for it"""
+        if not self._own(r):
+            t, k, p = self._default
+            return [(t, k, p, 1.0, self._seed, -1)] * r.n
+        s = r.sampling
+        t, k, p = _config(s)
+        if s.get("seed") is not None:
+            seed = int(s["seed"]) & 0xffffffff
+        else:
+            self._serial += 1
+            seed = (self._seed * 0x9E3779B1 + self._serial * 0x85EBCA77 + 0x27D4EB2F) & 0xffffffff
+        return [(t, k, p, _penalty(s), seed, j) for j in range(r.n)]
+
+    def _group_sampling(self, grp):
+        """the per-sequence entries of an admission, or None when every request of it runs under the batcher's configuration"""
+        if not any(self._own(r) for r in grp):
+            return None
+        return [e for r in grp for e in self._entries(r)]
+
+    def _sync_mode(self):
+        """the per-row step while a running row has parameters of its own (or always, per_row=True); the shared step otherwise.  Queued on the
+        current stream, in front of the next decode steps"""
+        want = self._force_per_row or any(self.row_own.get(row, False) for row in self.active)
+        if want != self._per_row:
+            self.engine.rows_per_row(want)
+            self._per_row = want
 
     def _mark(self):
         if self._ev is None:
@@ -140,6 +208,17 @@ class ContinuousBatcher:
                              f"(max_prefill_tokens {cfg.max_prefill_tokens}, max_patches {cfg.max_patches}, max_ctx {cfg.max_ctx})")
         if not 1 <= int(req.n) <= cfg.max_batch:          # its forks decode side by side: all n of them need a row
             raise ValueError(f"request of n = {req.n} sequences exceeds the engine's capacity (1 <= n <= max_batch {cfg.max_batch})")
+        if req.sampling is not None:                      # (refused here, not in the middle of a scheduling round by the engine)
+            s = req.sampling
+            t, k, p = _config(s)
+            if s.get("temperature") is not None and not float(s["temperature"]) >= 0:
+                raise ValueError(f"request sampling: temperature {s['temperature']} < 0")
+            if k > 1024:
+                raise ValueError(f"request sampling: top_k {k} > 1024 (the continuous batcher draws top-k <= 1024 on the device)")
+            if not 0 < p <= 1:
+                raise ValueError(f"request sampling: top_p {p} outside (0, 1]")
+            if not _penalty(s) > 0:
+                raise ValueError(f"request sampling: repetition_penalty {s.get('repetition_penalty')} <= 0")
         self.pending.append(req)
 
     def idle(self) -> bool:
@@ -180,7 +259,8 @@ class ContinuousBatcher:
                 pix = torch.cat([self.engine.patchify(im) for im in ims], dim=0)
                 emb = self.engine.vit_forward(pix, [g for r in grp for g in r.grids])
             t1 = self._mark()
-            self.engine.admit(rows, [r.ids for r in grp], [r.pos3 for r in grp], [r.max_new for r in grp], emb, fanout=self._fanout(grp))
+            self.engine.admit(rows, [r.ids for r in grp], [r.pos3 for r in grp], [r.max_new for r in grp], emb, fanout=self._fanout(grp),
+                              sampling=self._group_sampling(grp))
         except BaseException:
             self.free.extendleft(reversed(rows))
             raise
@@ -189,6 +269,7 @@ class ContinuousBatcher:
         for row, (r, j) in zip(rows, self._forks(grp)):
             self.active[row] = r
             self.row_fork[row] = j
+            self.row_own[row] = self._own(r)
         self.stats["admitted"] += n_seq
         self.stats["admitted_prompts"] += len(grp)
         self.stats["admissions"] += 1
@@ -371,7 +452,8 @@ class ContinuousBatcher:
                 pix = torch.cat([self.engine.patchify(im) for im in ims], dim=0)
                 emb = self.engine.vit_forward(pix, [g for r in grp for g in r.grids])
             t1 = self._mark()
-            self.engine.admit_stage(slots, [r.ids for r in grp], [r.pos3 for r in grp], [r.max_new for r in grp], emb, fanout=self._fanout(grp))
+            self.engine.admit_stage(slots, [r.ids for r in grp], [r.pos3 for r in grp], [r.max_new for r in grp], emb, fanout=self._fanout(grp),
+                                    sampling=self._group_sampling(grp))
             self._span("vit" + shared, t0, t1)
             self._span("prefill" + shared, t1, self._mark())
             ev = torch.cuda.Event(enable_timing=cal)
@@ -398,6 +480,7 @@ class ContinuousBatcher:
             self.active[row] = r
             self.row_slot[row] = slot
             self.row_fork[row] = j
+            self.row_own[row] = self._own(r)
             self._cnt_last[row] = 0
         dead = [row for row, r in zip(rows, grp[:k]) if r.aborted]      # aborted while they waited for a row: stop before the first step
         if dead:
@@ -439,6 +522,7 @@ class ContinuousBatcher:
                 c0.record(s)
             t0 = self._mark()
             self._set_cus(self.streams.decode_cus if s is self.streams.decode else 0)
+            self._sync_mode()
             self.engine.rows_step(self.steps_per_poll, self.eos, self.pad_id)
             self._span("decode_shared" if shares else "decode", t0, self._mark())
             if cal or cal_sh:
@@ -450,6 +534,7 @@ class ContinuousBatcher:
                     self._cal_dec_sh = (c0, c1, self.steps_per_poll, self._share, self.staged[2])
         self.stats["steps"] += self.steps_per_poll
         self.stats["steps_shared"] += self.steps_per_poll if shares else 0
+        self.stats["steps_per_row"] += self.steps_per_poll if self._per_row else 0
         self._deliver(on_complete)                     # the rows that finished in the previous round (their callbacks may submit new requests)
         if self.staged is None and self.pending and self.free_slots:
             self._stage()                              # the host side of the next admission is prepared while the chunk above runs
@@ -495,6 +580,7 @@ class ContinuousBatcher:
                 ev.record(s)
                 self._deferred.append(([(self.active.pop(r), self.row_fork.pop(r, 0)) for r in rows], counts, buf, ev))
                 for row in rows:
+                    self.row_own.pop(row, None)
                     self.free.append(row)
                     self.free_slots.append(self.row_slot.pop(row))
             if not self.active:          # nothing will be queued behind them: deliver now
@@ -547,12 +633,15 @@ class ContinuousBatcher:
         if not self.active:
             return
         t0 = self._mark()
+        self._sync_mode()
         self.engine.rows_step(self.steps_per_poll, self.eos, self.pad_id)
         self._span("decode", t0, self._mark())
         self.stats["steps"] += self.steps_per_poll
+        self.stats["steps_per_row"] += self.steps_per_poll if self._per_row else 0
         fin, cnt = self._poll()
         for row in [r for r in self.active if fin[r]]:
             req = self.active.pop(row)
+            self.row_own.pop(row, None)
             toks = self.engine.row_tokens(row, int(cnt[row])).cpu().tolist()
             self.free.append(row)
             self._report(req, self.row_fork.pop(row, 0), toks, on_complete)
