@@ -97,6 +97,26 @@ const SrSwitches& sr_switches() {
     return g_sw;
 }
 
+// The captured forms of one decode step (the slots of sr_engine::graphs)
+enum StepKind {
+    STEP_GREEDY,            // sr_decode, sr_rows_step: k_step reduces the LM head's arg-max partials
+    STEP_CALLER_GREEDY,     // sr_decode_step feeding the engine's greedy token
+    STEP_CALLER_CHOSEN,     // sr_decode_step feeding the caller's token (d_chosen)
+    STEP_SAMPLED,           // sr_decode_sample: bookkeeping + forward + k_sample
+    STEP_BEAM,              // sr_decode_beam: bookkeeping + forward + row statistics + select + KV suffix copies
+    STEP_ROWS_SAMPLED,      // sr_rows_step under sr_rows_sampling
+    STEP_ROWS_PERROW,       // sr_rows_step under sr_rows_per_row
+    STEP_KINDS
+};
+// everything a captured step bakes in BY VALUE (step_key fills it from the step's description); compared as a whole with memcmp
+struct StepKey {
+    int B, n_eos, pad_id;
+    int top_k; float inv_temp, top_p, rep_penalty; unsigned seed;      // the sampled kinds
+    int W, K, max_new; float length_penalty;                           // beam
+};
+static_assert(sizeof(StepKey) == 12 * 4, "no padding");
+struct StepGraph { hipGraphExec_t exec = nullptr; StepKey key{}; };
+
 struct sr_engine {
     sr_config c;
     // derived geometry
@@ -154,38 +174,30 @@ struct sr_engine {
     char* d_stage = nullptr;
     hipEvent_t ev_copy = nullptr;
     bool copy_pending = false;
-    // ---- decode graph cache
-    hipGraphExec_t graph[2] = {nullptr, nullptr};     // [px_mode]: the decode step on the whole chip / on a CU-limited stream (x-stationary GEMVs, sr_rows_set_cus)
+    // ---- decode graph cache (step_graph): [step kind][px_mode], px_mode = the decode step on the whole chip / on a CU-limited stream
+    // (x-stationary GEMVs, sr_rows_set_cus); the continuous batcher alternates between the two, so both forms stay cached
+    StepGraph graphs[STEP_KINDS][2];
     int px_mode = 0;
     int device = 0;                     // the GPU the workspace lives on: every C-ABI entry makes it current (per-thread HIP state)
     hipStream_t cap_stream = nullptr;   // used only to CAPTURE the decode step (the caller's stream may be the null stream)
-    int graph_B[2] = {-1, -1}, graph_neos[2] = {-1, -1}, graph_pad[2] = {0, 0};
-    hipGraphExec_t step_graph[2] = {nullptr, nullptr};   // sr_decode_step: [0] engine-greedy token, [1] caller-chosen token
-    int step_graph_B[2] = {-1, -1}, step_graph_px[2] = {0, 0};
     long long *d_chosen = nullptr, *d_next = nullptr, *d_sampled = nullptr;
     unsigned* d_seen = nullptr;    // [MAXB][seen_words] token bitmask for the repetition penalty
     int seen_words = 0;
     // continuous batching with sampling (sr_rows_sampling): parameters shared by all rows; 0 temperature = greedy
     float rows_temp = 0.f, rows_topp = 1.f; int rows_topk = 0; unsigned rows_seed = 0, adm_count = 0;
     long long* d_adm_pick = nullptr;
-    struct RowsGraph { hipGraphExec_t g = nullptr; int neos = -1, pad = 0, topk = 0; float it = 0.f, topp = 0.f; unsigned seed = 0; } rgraph[2];      // [px_mode]
     // per-request sampling in the continuous batcher (sr_rows_per_row, sr_admit_sampling / sr_admit_stage_sampling): allocated on first use.
     // rp_rows [MAXB] / rp_stage [MAXB]: the parameter table of the batch rows / of the staged sequences; rp_seen [n_slots][seen_words]: one
     // repetition-penalty bitmap per KV slot; h_rp: pinned upload buffer of the staged entries
     void* rp_mem = nullptr; RowParams *rp_rows = nullptr, *rp_stage = nullptr, *h_rp = nullptr; unsigned* rp_seen = nullptr;
     bool rows_perrow = false;       // sr_rows_step replays the per-row graph
     bool staged_rp = false;         // the staged admission drew its first tokens under its table entries (and marked its slots' bitmaps)
-    struct PerRowGraph { hipGraphExec_t g = nullptr; int neos = -1, pad = 0; } pgraph[2];      // [px_mode]
-    hipGraphExec_t sgraph = nullptr;      // sampled decode step: bookkeeping + forward + k_sample
-    int sg_B = -1, sg_neos = -1, sg_pad = 0, sg_topk = 0, sg_px = 0; float sg_it = 0.f, sg_topp = 0.f, sg_rp = 0.f; unsigned sg_seed = 0;
     int prefilled_B = 0;
     int pre_len[MAXB], pre_slot[MAXB], pre_pos[MAXB];   // static prefill: every sequence's length, KV slot and last position (sr_decode_beam)
     // beam search (sr_decode_beam): device state allocated on first use, freed on destroy
     void* beam_mem = nullptr;
     BeamPart* bm_part = nullptr; float* bm_scores = nullptr; long long* bm_tok = nullptr; BeamTrace* bm_trace = nullptr; BeamFin* bm_fin = nullptr;
     int *bm_fin_n = nullptr, *bm_done = nullptr, *bm_stop = nullptr, *bm_eos = nullptr, *bm_plen = nullptr, *bm_fan = nullptr; int4* bm_copies = nullptr;
-    hipGraphExec_t bgraph = nullptr;      // beam step: bookkeeping + forward + row statistics + select + KV suffix copies
-    int bg_B = -1, bg_W = 0, bg_K = 0, bg_neos = -1, bg_pad = 0, bg_max_new = 0, bg_px = 0; float bg_lp = 0.f;
     int h_ctx_hi = 0;              // longest context any slot can have reached (prefill length + decode steps issued)
     // ---- bookkeeping
     std::map<std::string, bool> loaded;
@@ -709,6 +721,142 @@ int enqueue_step(sr_engine* e, int B, int n_eos, int pad_id, const int* forced, 
     return 0;
 }
 
+// k_sample's arguments for n draws, the engine-constant part: the decode logits at every row's step -> d_sampled, with the LM head's
+// block maxima; or (admission) the admission logits -> d_adm_pick.  The scalars start as the placeholders of the per-row table forms
+SampleArgs sample_args(const sr_engine* e, int n, bool admission) {
+    const sr_config& c = e->c;
+    SampleArgs a{};
+    a.V = c.t_vocab; a.B = n; a.seen_words = e->seen_words;
+    a.inv_temp = 1.0f; a.top_k = 1; a.top_p = 1.0f; a.rep_penalty = 1.0f;
+    if (admission) { a.logits = e->d_logits_adm; a.out = e->d_adm_pick; return a; }
+    const int hn = fused_norms(e, n) ? 1 : 0;
+    a.logits = e->d_logits; a.step = e->d_step; a.out = e->d_sampled;
+    a.blk_max = e->d_amax_val; a.n_blk = gemv_f32_blocks(c.t_vocab, n, c.t_hidden, hn); a.blk_rows = gemv_f32_block_rows(c.t_vocab, n, c.t_hidden, hn);
+    return a;
+}
+
+// ---- one decode step: k_step consumes every row's pending token (log, eos / limit bookkeeping, next input embedding), the forward
+// runs, and the tail leaves the next pending tokens where the next k_step reads them.  The captured AND the eager form of every
+// variant are enqueue_decode_step on this description
+struct Step {
+    int B, n_eos, pad_id;
+    const int* forced;            // teacher-forced tokens (sr_decode)
+    const long long* chosen;      // the pending tokens; null: the arg-max of the LM head's partials
+    // repetition-penalty bitmaps, marked with the pending tokens: MARK_ROWS before k_step (rp_seen: per KV slot, unfinished rows),
+    // MARK_CHOSEN after it (d_seen: per row)
+    enum { MARK_NONE, MARK_ROWS, MARK_CHOSEN } mark;
+    enum { TAIL_NONE, TAIL_SAMPLE, TAIL_NEXT_IDS, TAIL_BEAM } tail;
+    SampleArgs sample;                                   // TAIL_SAMPLE
+    const BeamArgs* beam; const KvSuffixArgs* suffix;    // TAIL_BEAM: row statistics, group select, KV suffix copies
+};
+Step make_step(int B, int n_eos, int pad_id, const long long* chosen) {
+    Step st{};
+    st.B = B; st.n_eos = n_eos; st.pad_id = pad_id; st.chosen = chosen;
+    return st;
+}
+StepKey step_key(const Step& st) {
+    StepKey k{};
+    k.B = st.B; k.n_eos = st.n_eos; k.pad_id = st.pad_id;
+    if (st.tail == Step::TAIL_SAMPLE) {
+        k.top_k = st.sample.top_k; k.inv_temp = st.sample.inv_temp; k.top_p = st.sample.top_p; k.rep_penalty = st.sample.rep_penalty; k.seed = st.sample.seed;
+    } else if (st.tail == Step::TAIL_BEAM) {      // (k_step runs without eos there: the select kernel owns them)
+        k.n_eos = st.beam->n_eos; k.W = st.beam->W; k.K = st.beam->K; k.max_new = st.beam->max_new; k.length_penalty = st.beam->lp;
+    }
+    return k;
+}
+
+int enqueue_step_tail(sr_engine* e, const Step& st, hipStream_t q) {
+    const sr_config& c = e->c;
+    if (st.tail == Step::TAIL_SAMPLE) SR_TRY(launch_sample(q, st.sample));
+    if (st.tail == Step::TAIL_NEXT_IDS)
+        SR_TRY(launch_next_ids(q, e->d_amax_val, e->d_amax_idx, gemv_f32_blocks(c.t_vocab, st.B, c.t_hidden, fused_norms(e, st.B) ? 1 : 0), st.B, e->d_next));
+    if (st.tail == Step::TAIL_BEAM) {
+        SR_TRY(launch_beam_rowstats(q, *st.beam));
+        SR_TRY(launch_beam_select(q, *st.beam));
+        SR_TRY(launch_kv_suffix(q, *st.suffix));
+    }
+    return 0;
+}
+
+// logits_copy: eager traced runs keep the step's float32 logits [B, V]
+int enqueue_decode_step(sr_engine* e, const Step& st, hipStream_t q, float* logits_copy = nullptr) {
+    if (st.mark == Step::MARK_ROWS) SR_TRY(launch_mark_rows(q, st.chosen, e->d_finished, e->d_slots, e->rp_seen, e->seen_words, st.B));
+    if (int rc = enqueue_step(e, st.B, st.n_eos, st.pad_id, st.forced, q, st.chosen)) return rc;
+    if (st.mark == Step::MARK_CHOSEN) SR_TRY(launch_mark_chosen(q, st.chosen, e->d_seen, e->seen_words, st.B));
+    if (int rc = enqueue_decode_forward(e, st.B, q)) return rc;
+    if (logits_copy) SR_TRY((int)hipMemcpyAsync(logits_copy, e->d_logits, (size_t)st.B * e->c.t_vocab * 4, hipMemcpyDeviceToDevice, q));
+    return enqueue_step_tail(e, st, q);
+}
+
+// The step as a ready graph: slot [kind][px_mode] of the cache, reused while its key matches, otherwise captured again on cap_stream
+int step_graph(sr_engine* e, StepKind kind, const Step& st, hipGraphExec_t* exec) {
+    StepGraph& sg = e->graphs[kind][e->px_mode];
+    const StepKey key = step_key(st);
+    if (sg.exec == nullptr || memcmp(&sg.key, &key, sizeof key) != 0) {
+        if (sg.exec) { (void)hipGraphExecDestroy(sg.exec); sg.exec = nullptr; }
+        hipGraph_t g = nullptr;
+        SR_TRY((int)hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
+        const int rc = enqueue_decode_step(e, st, e->cap_stream);
+        hipError_t er = hipStreamEndCapture(e->cap_stream, &g);
+        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+        SR_TRY((int)er);
+        er = hipGraphInstantiate(&sg.exec, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        SR_TRY((int)er);
+        sg.key = key;
+    }
+    *exec = sg.exec;
+    return 0;
+}
+
+// The step loop of the static decodes: steps first .. max_new - 1 (replays of `exec`, or eager launches that keep each step's logits
+// from `trace` on), stopping once all n_flags device flags are set (read every 16th step; d_flags null: never).  record_last: step
+// max_new - 1 only records its token.  -> *done = steps issued, counted from 0
+int run_steps(sr_engine* e, const Step& st, hipGraphExec_t exec, int first, int max_new, bool record_last, float* trace, const int* d_flags,
+              int n_flags, hipStream_t s, int* done) {
+    const size_t BV = (size_t)st.B * e->c.t_vocab;
+    std::vector<int> flags(n_flags);
+    *done = first;
+    for (int i = first; i < max_new; ++i) {
+        if (record_last && i == max_new - 1) {
+            if (int rc = enqueue_step(e, st.B, st.n_eos, st.pad_id, st.forced, s, st.chosen)) return rc;
+            *done = max_new;
+            break;
+        }
+        if (exec) SR_TRY((int)hipGraphLaunch(exec, s));
+        else if (int rc = enqueue_decode_step(e, st, s, trace ? trace + (size_t)(i - first) * BV : nullptr)) return rc;
+        *done = i + 1;
+        if (d_flags && (i % 16) == 15) {
+            SR_TRY((int)hipMemcpyAsync(flags.data(), d_flags, n_flags * 4, hipMemcpyDeviceToHost, s));
+            SR_TRY((int)hipStreamSynchronize(s));
+            bool all = true;
+            for (int f : flags) all &= f != 0;
+            if (all) break;
+        }
+    }
+    return 0;
+}
+
+// sr_decode / sr_decode_sample: the steps (early exit once every sequence has emitted an eos token), then the token log
+// [B][max_new_tokens] -> caller layout [B][max_new]; unwritten positions read as pad
+int decode_static(sr_engine* e, const Step& st, hipGraphExec_t exec, int max_new, float* trace, int32_t* tokens_out, hipStream_t s, int* steps_done) {
+    const sr_config& c = e->c;
+    int done = 0;
+    if (int rc = run_steps(e, st, exec, 0, max_new, true, trace, st.n_eos ? e->d_finished : nullptr, st.B, s, &done)) return rc;
+    if (done < max_new) {
+        // fill the tail of the device log with pad before copying out
+        std::vector<int> padrow(max_new, st.pad_id);
+        for (int b = 0; b < st.B; ++b)
+            SR_TRY((int)hipMemcpyAsync(e->d_tokens + (size_t)b * c.max_new_tokens + done, padrow.data(), (max_new - done) * 4, hipMemcpyHostToDevice, s));
+        SR_TRY((int)hipStreamSynchronize(s));
+    }
+    SR_TRY((int)hipMemcpy2DAsync(tokens_out, (size_t)max_new * 4, e->d_tokens, (size_t)c.max_new_tokens * 4, (size_t)max_new * 4, st.B,
+                                 hipMemcpyDeviceToDevice, s));
+    SR_TRY((int)hipStreamSynchronize(s));
+    if (steps_done) *steps_done = done;
+    return 0;
+}
+
 }  // namespace
 
 // counter block of the x-stationary GEMVs for the op-level entry points (engines own theirs): 8 ticket shards + done count + the CU limit, 64 B apart
@@ -804,13 +952,8 @@ int sr_engine_create(const sr_config* cfg, void* workspace, size_t workspace_byt
 int sr_engine_destroy(sr_engine* e) {
     enter(e);
     if (!e) return 0;
-    for (auto g : e->graph) if (g) (void)hipGraphExecDestroy(g);
-    for (auto g : e->step_graph) if (g) (void)hipGraphExecDestroy(g);
-    if (e->sgraph) (void)hipGraphExecDestroy(e->sgraph);
-    if (e->bgraph) (void)hipGraphExecDestroy(e->bgraph);
+    for (auto& kind : e->graphs) for (auto& g : kind) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (e->beam_mem) (void)hipFree(e->beam_mem);
-    for (auto& r : e->rgraph) if (r.g) (void)hipGraphExecDestroy(r.g);
-    for (auto& r : e->pgraph) if (r.g) (void)hipGraphExecDestroy(r.g);
     if (e->rp_mem) (void)hipFree(e->rp_mem);
     if (e->h_rp) (void)hipHostFree(e->h_rp);
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
@@ -1063,15 +1206,35 @@ static int commit_admission(sr_engine* e, const int32_t* rows, int n, hipStream_
     return 0;
 }
 
-// `commit`: admission only -- install the rows right away (rows = slots: the plain sr_admit); false = stage, sr_admit_commit installs later.
-// Admission only, `fanout` / `fork_slots` (both null: one sequence per prompt): prompt b becomes fanout[b] staged sequences (prompt-major) whose
-// KV slots are fork_slots (sum of fanout entries); it is prefilled once into slots[b] (= its first fork's slot), its LM head runs once, and
-// one k_kv_fanout launch copies every prompt's prefix into the slots of its other forks.  Each staged sequence draws its own first token.
-static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* slots, int B,
-                        const void* image_embeds, int n_image_rows, float* logits_out, void* stream, const int32_t* limits,
-                        float* all_logits_out = nullptr, bool commit = true, const int32_t* fanout = nullptr, const int32_t* fork_slots = nullptr,
-                        const sr_sampling* smp = nullptr) {
+// the packed prompts as every prefill entry point receives them
+struct Prompts {
+    const int64_t *ids, *pos3; const int32_t* seq_lens; int B;
+    const void* image_embeds; int n_image_rows;
+    float* logits_out;                      // optional: float32 [B, V] of the last positions
+    void* stream;
+};
+struct PrefillArgs {
+    Prompts p;
+    const int32_t* slots = nullptr;         // the KV slot prompt b is prefilled into
+    float* all_logits_out = nullptr;        // static only (sr_forward_logits): float32 logits of every position
+    // `admission`: into the continuous batch (row state untouched until the commit, admission-owned scratch) instead of a static batch
+    // that (re)initialises rows 0..B-1.  The fields below are read for an admission only
+    bool admission = false;
+    const int32_t* limits = nullptr;        // max_new per prompt
+    bool commit = false;                    // install the rows right away (rows = slots: the plain sr_admit); false = stage, sr_admit_commit installs later
+    // `fanout` / `fork_slots` (both null: one sequence per prompt): prompt b becomes fanout[b] staged sequences (prompt-major) whose
+    // KV slots are fork_slots (sum of fanout entries); it is prefilled once into slots[b] (= its first fork's slot), its LM head runs once, and
+    // one k_kv_fanout launch copies every prompt's prefix into the slots of its other forks.  Each staged sequence draws its own first token.
+    const int32_t *fanout = nullptr, *fork_slots = nullptr;
+    const sr_sampling* sampling = nullptr;  // optional: one entry per staged sequence (the per-row table exists: ensure_row_params)
+};
+
+static int prefill_impl(sr_engine* e, const PrefillArgs& pa) {
     enter(e);
+    const auto& [ids, pos3, seq_lens, B, image_embeds, n_image_rows, logits_out, stream] = pa.p;
+    const int32_t* slots = pa.slots;
+    const bool admission = pa.admission;
+    const sr_sampling* smp = pa.sampling;
     if (!e || !ids || !pos3 || !seq_lens || !slots) return fail(e, -22, "sr_prefill: null argument");
     char miss[160];
     if (sr_weights_missing(e, miss, sizeof miss)) return fail(e, -61, "weights missing, e.g. '%s'", miss);
@@ -1120,11 +1283,11 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
             h_slot[t] = slots[b];
             h_idx[t] = i;
         }
-        if (!limits) { e->pre_len[b] = S; e->pre_slot[b] = slots[b]; e->pre_pos[b] = (int)maxpos; }
+        if (!admission) { e->pre_len[b] = S; e->pre_slot[b] = slots[b]; e->pre_pos[b] = (int)maxpos; }
         for (int q0 = 0; q0 < S; q0 += 64)
             h_work[n_work++] = AttnWork{t0 + q0, S, q0, slots[b] * KVH * c.max_ctx, (long long)slots[b] * KVH * 128 * c.max_ctx};
         h_last[b] = t0 + S - 1;
-        const int f = fanout ? fanout[b] : 1;
+        const int f = pa.fanout ? pa.fanout[b] : 1;
         if (f > 1) {
             int* g = h_grp + 4 * n_groups++;
             g[0] = slots[b]; g[1] = S; g[2] = n_seq + 1; g[3] = f - 1;
@@ -1135,8 +1298,8 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
             h_state[n_seq] = S;                     // keys in the cache; k_step_advance adds the new token before each forward
             h_state[MAXB + n_seq] = (int)maxpos;      // decode positions continue at max+1 on all three axes
                                                     // (reference rule: roll/utils/functionals.py:816-818)
-            h_state[2 * MAXB + n_seq] = fork_slots ? fork_slots[n_seq] : slots[b];
-            h_state[3 * MAXB + n_seq] = limits ? limits[b] : 0x7f7f7f7f;
+            h_state[2 * MAXB + n_seq] = pa.fork_slots ? pa.fork_slots[n_seq] : slots[b];
+            h_state[3 * MAXB + n_seq] = admission ? pa.limits[b] : 0x7f7f7f7f;
         }
         t0 += S;
     }
@@ -1146,7 +1309,7 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
     if (total > e->stage_bytes) return fail(e, -12, "control staging too small");
     // once the per-row table exists, every admission stages its sequences' entries (its own, or the shared configuration restated)
     // (h_rp is free again: stage_begin waited for the event recorded behind the previous upload, which follows this copy on its stream)
-    const bool rp_stage = limits && e->rp_mem;
+    const bool rp_stage = admission && e->rp_mem;
     if (rp_stage) {
         for (int i = 0; i < n_seq; ++i) {
             RowParams p = default_params(e);
@@ -1164,7 +1327,7 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
     SR_TRY((int)hipMemcpyAsync(e->t_idx, dmirror(h_idx), (size_t)n_tok * 4, hipMemcpyDeviceToDevice, s));
     SR_TRY((int)hipMemcpyAsync(e->t_lastrow, dmirror(h_last), MAXB * 4, hipMemcpyDeviceToDevice, s));
     SR_TRY((int)hipMemcpyAsync(e->t_work, dmirror(h_work), n_work * sizeof(AttnWork), hipMemcpyDeviceToDevice, s));
-    if (!limits) {       // static batch: rows 0..B-1 are (re)initialised, all other rows are dropped
+    if (!admission) {       // static batch: rows 0..B-1 are (re)initialised, all other rows are dropped
         SR_TRY((int)hipMemcpyAsync(e->d_ctx_len, dmirror(h_state), MAXB * 4, hipMemcpyDeviceToDevice, s));
         SR_TRY((int)hipMemcpyAsync(e->d_pos, dmirror(h_state + MAXB), MAXB * 4, hipMemcpyDeviceToDevice, s));
         SR_TRY((int)hipMemcpyAsync(e->d_slots, dmirror(h_state + 2 * MAXB), MAXB * 4, hipMemcpyDeviceToDevice, s));
@@ -1184,7 +1347,7 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
     const int H = c.t_hidden, QD = c.t_heads * 128;
     SR_TRY(launch_embed(s, e->t_src, e->embed, static_cast<const bf16_t*>(image_embeds), e->t_x, n_tok, H, 1));
     const float scale = (float)(1.0 / sqrt(128.0));
-    const bool splitk = !limits && prefill_splitk(e, n_tok);
+    const bool splitk = !admission && prefill_splitk(e, n_tok);
     bool pending = false;        // split-K: the down-projection's slabs have not been added to t_x yet
     for (int l = 0; l < c.t_layers; ++l) {
         const LmLayerW& w = e->ll[l];
@@ -1222,15 +1385,15 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
     // last position of every sequence -> final norm -> tied LM head (hf:1386-1387) -> greedy token
     // (split-K: the last down-projection's slabs still have to reach t_x; the norm output is only used by the all-positions path)
     if (pending) SR_TRY(launch_resid_rmsnorm(s, e->t_x, e->t_slabs, SPLITK_KS, e->final_norm, e->t_xn, n_tok, H, c.t_rms_eps, 0, 1));
-    if (all_logits_out) {       // every position: final norm over all rows, tied LM head as an MFMA GEMM with float32 output
+    if (pa.all_logits_out) {       // every position: final norm over all rows, tied LM head as an MFMA GEMM with float32 output
         if (!pending) SR_TRY(launch_rmsnorm(s, e->t_x, e->final_norm, e->t_xn, n_tok, H, c.t_rms_eps, 0, 1));
-        if (int rc = gemm(e, s, e->t_xn, H, e->embed, n_tok, c.t_vocab, H, all_logits_out, c.t_vocab, nullptr, nullptr, nullptr, EPI_F32, 1)) return rc;
+        if (int rc = gemm(e, s, e->t_xn, H, e->embed, n_tok, c.t_vocab, H, pa.all_logits_out, c.t_vocab, nullptr, nullptr, nullptr, EPI_F32, 1)) return rc;
     }
     // (an admission keeps to scratch of its own -- d_xadm / d_xadm_n, the *_adm logits and partials -- because it may run on another
     // stream while the rows decode)
-    bf16_t* xl = limits ? e->d_xadm : e->d_xa;
+    bf16_t* xl = admission ? e->d_xadm : e->d_xa;
     SR_TRY(launch_gather_rows(s, e->t_x, e->t_lastrow, xl, B, H));
-    if (!limits) {
+    if (!admission) {
         if (int rc = enqueue_lm_head(e, B, xl, e->d_xb, false, s)) return rc;
         if (logits_out) SR_TRY((int)hipMemcpyAsync(logits_out, e->d_logits, (size_t)B * c.t_vocab * 4, hipMemcpyDeviceToDevice, s));
         e->h_ctx_hi = 0;
@@ -1257,14 +1420,16 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
     if (rp_stage) {                // per-row table: each staged sequence's slot bitmap = its prompt, then its first token under its own entry
         SR_TRY(launch_mark_staged(s, e->t_src, e->t_lastrow, n_groups ? e->d_fan : nullptr, e->d_adm_slots, e->rp_seen, e->seen_words, n_seq));
         // (salt: the shared path's seed of this admission for the entries keyed by the row -- sr_rows_sampling's draw below, restated)
-        SampleArgs sa{e->d_logits_adm, c.t_vocab, n_seq, 1.0f, 1, 1.0f, 1.0f, e->rp_seen, e->seen_words,
-                      e->rows_temp > 0.f ? 0x9E3779B9u * ++e->adm_count : 0u, nullptr, e->d_adm_pick, nullptr, 0, 0, row_map};
-        sa.params = e->rp_stage;
-        sa.seen_slot = e->d_adm_slots;
+        SampleArgs sa = sample_args(e, n_seq, true);
+        sa.row_map = row_map;
+        sa.seen = e->rp_seen; sa.params = e->rp_stage; sa.seen_slot = e->d_adm_slots;
+        sa.seed = e->rows_temp > 0.f ? 0x9E3779B9u * ++e->adm_count : 0u;
         SR_TRY(launch_sample(s, sa));
     } else if (e->rows_temp > 0.f) {      // sampling mode: the first token of the new rows is drawn from the admission logits
-        SampleArgs sa{e->d_logits_adm, c.t_vocab, n_seq, 1.0f / e->rows_temp, e->rows_topk, e->rows_topp, 1.0f, nullptr, e->seen_words,
-                      e->rows_seed ^ (0x9E3779B9u * ++e->adm_count), nullptr, e->d_adm_pick, nullptr, 0, 0, row_map};
+        SampleArgs sa = sample_args(e, n_seq, true);
+        sa.row_map = row_map;
+        sa.inv_temp = 1.0f / e->rows_temp; sa.top_k = e->rows_topk; sa.top_p = e->rows_topp;
+        sa.seed = e->rows_seed ^ (0x9E3779B9u * ++e->adm_count);
         SR_TRY(launch_sample(s, sa));
     }
     if (n_groups) {                // the prompts' KV prefixes into the slots of their other forks (d_adm_slots holds every fork's slot in staged order)
@@ -1275,13 +1440,16 @@ static int prefill_impl(sr_engine* e, const int64_t* ids, const int64_t* pos3, c
     e->staged_n = n_seq;
     e->staged_off = 0;
     e->staged_rp = rp_stage;
-    if (commit) return commit_admission(e, fork_slots ? fork_slots : slots, n_seq, s);
+    if (pa.commit) return commit_admission(e, pa.fork_slots ? pa.fork_slots : slots, n_seq, s);
     return 0;
 }
 
 int sr_prefill(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* slots, int B,
                const void* image_embeds, int n_image_rows, float* logits_out, void* stream) {
-    return prefill_impl(e, ids, pos3, seq_lens, slots, B, image_embeds, n_image_rows, logits_out, stream, nullptr);
+    PrefillArgs pa;
+    pa.p = Prompts{ids, pos3, seq_lens, B, image_embeds, n_image_rows, logits_out, stream};
+    pa.slots = slots;
+    return prefill_impl(e, pa);
 }
 
 int sr_forward_logits(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, int B, const void* image_embeds,
@@ -1290,7 +1458,11 @@ int sr_forward_logits(sr_engine* e, const int64_t* ids, const int64_t* pos3, con
     if (!e || B < 1 || B > MAXB) return fail(e, -22, "sr_forward_logits: bad batch");
     int32_t slots[MAXB];
     for (int b = 0; b < B; ++b) slots[b] = b;
-    return prefill_impl(e, ids, pos3, seq_lens, slots, B, image_embeds, n_image_rows, nullptr, stream, nullptr, all_logits_out);
+    PrefillArgs pa;
+    pa.p = Prompts{ids, pos3, seq_lens, B, image_embeds, n_image_rows, /*logits_out*/ nullptr, stream};
+    pa.slots = slots;
+    pa.all_logits_out = all_logits_out;
+    return prefill_impl(e, pa);
 }
 
 // ---- continuous batching: batch rows with independent lifecycles (row index = KV slot); a decode step always runs all
@@ -1385,16 +1557,35 @@ static void first_forks(const int32_t* fanout, const int32_t* dst, int n, int32_
     for (int i = 0, k = 0; i < n; k += fanout ? fanout[i] : 1, ++i) out[i] = dst[k];
 }
 
+// Every admission entry point: `fn` names it in refusals; `dst` = one destination per staged sequence, prompt-major: batch rows
+// (installed right away, row r uses KV slot r) or spare KV slots (staged: sr_admit_commit installs later).  `sampling` comes from the
+// *_sampling entries only: they create the per-row table on first use, after which EVERY admission stages table entries
+enum AdmitTo { TO_ROWS, TO_SPARE_SLOTS };
+static int admit(sr_engine* e, const char* fn, AdmitTo to, const Prompts& p, const int32_t* fanout, const int32_t* dst, const int32_t* max_new,
+                 const sr_sampling* sampling) {
+    enter(e);
+    if (!e || !dst || !max_new || !p.seq_lens) return fail(e, -22, "%s: null argument", fn);
+    const bool rows = to == TO_ROWS;
+    const int total = check_fanout(e, fn, p.seq_lens, fanout, dst, p.B, rows ? e->c.max_batch : e->n_slots, rows ? "row" : "KV slot", max_new);
+    if (total < 0) return total;
+    if (sampling) {
+        if (int rc = check_sampling(e, fn, sampling, total)) return rc;
+        SR_TRY(ensure_row_params(e, (hipStream_t)p.stream));
+    }
+    int32_t first[MAXB];
+    first_forks(fanout, dst, p.B, first);
+    PrefillArgs pa;
+    pa.p = p;
+    pa.slots = first;
+    pa.admission = true; pa.limits = max_new; pa.commit = rows;
+    pa.fanout = fanout; pa.fork_slots = dst; pa.sampling = sampling;
+    return prefill_impl(e, pa);
+}
+
+// (sr_admit_fanout and sr_admit_stage_fanout report themselves under the names of their all-ones forms)
 int sr_admit_fanout(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* fanout, const int32_t* rows,
                     const int32_t* max_new, int n, const void* image_embeds, int n_image_rows, float* logits_out, void* stream) {
-    enter(e);
-    if (!e || !rows || !max_new || !seq_lens) return fail(e, -22, "sr_admit: null argument");
-    const int total = check_fanout(e, "sr_admit", seq_lens, fanout, rows, n, e->c.max_batch, "row", max_new);
-    if (total < 0) return total;
-    int32_t first[MAXB];
-    first_forks(fanout, rows, n, first);
-    return prefill_impl(e, ids, pos3, seq_lens, first, n, image_embeds, n_image_rows, logits_out, stream, max_new, nullptr, true,     // row r uses KV slot r
-                        fanout, rows);
+    return admit(e, "sr_admit", TO_ROWS, Prompts{ids, pos3, seq_lens, n, image_embeds, n_image_rows, logits_out, stream}, fanout, rows, max_new, nullptr);
 }
 
 int sr_admit(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* rows, const int32_t* max_new,
@@ -1409,13 +1600,8 @@ int sr_admit(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_
 int sr_admit_stage_fanout(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* fanout,
                           const int32_t* kv_slots, const int32_t* max_new, int n, const void* image_embeds, int n_image_rows, float* logits_out,
                           void* stream) {
-    enter(e);
-    if (!e || !kv_slots || !max_new || !seq_lens) return fail(e, -22, "sr_admit_stage: null argument");
-    const int total = check_fanout(e, "sr_admit_stage", seq_lens, fanout, kv_slots, n, e->n_slots, "KV slot", max_new);
-    if (total < 0) return total;
-    int32_t first[MAXB];
-    first_forks(fanout, kv_slots, n, first);
-    return prefill_impl(e, ids, pos3, seq_lens, first, n, image_embeds, n_image_rows, logits_out, stream, max_new, nullptr, false, fanout, kv_slots);
+    return admit(e, "sr_admit_stage", TO_SPARE_SLOTS, Prompts{ids, pos3, seq_lens, n, image_embeds, n_image_rows, logits_out, stream}, fanout, kv_slots, max_new,
+                 nullptr);
 }
 
 int sr_admit_stage(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* kv_slots, const int32_t* max_new,
@@ -1426,31 +1612,16 @@ int sr_admit_stage(sr_engine* e, const int64_t* ids, const int64_t* pos3, const 
 int sr_admit_stage_sampling(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* fanout,
                             const int32_t* kv_slots, const int32_t* max_new, const sr_sampling* sampling, int n, const void* image_embeds,
                             int n_image_rows, float* logits_out, void* stream) {
-    enter(e);
-    if (!e || !kv_slots || !max_new || !seq_lens || !sampling) return fail(e, -22, "sr_admit_stage_sampling: null argument");
-    const int total = check_fanout(e, "sr_admit_stage_sampling", seq_lens, fanout, kv_slots, n, e->n_slots, "KV slot", max_new);
-    if (total < 0) return total;
-    if (int rc = check_sampling(e, "sr_admit_stage_sampling", sampling, total)) return rc;
-    SR_TRY(ensure_row_params(e, (hipStream_t)stream));
-    int32_t first[MAXB];
-    first_forks(fanout, kv_slots, n, first);
-    return prefill_impl(e, ids, pos3, seq_lens, first, n, image_embeds, n_image_rows, logits_out, stream, max_new, nullptr, false, fanout, kv_slots,
-                        sampling);
+    if (!sampling) return fail(e, -22, "sr_admit_stage_sampling: null argument");
+    return admit(e, "sr_admit_stage_sampling", TO_SPARE_SLOTS, Prompts{ids, pos3, seq_lens, n, image_embeds, n_image_rows, logits_out, stream}, fanout, kv_slots,
+                 max_new, sampling);
 }
 
 int sr_admit_sampling(sr_engine* e, const int64_t* ids, const int64_t* pos3, const int32_t* seq_lens, const int32_t* fanout, const int32_t* rows,
                       const int32_t* max_new, const sr_sampling* sampling, int n, const void* image_embeds, int n_image_rows, float* logits_out,
                       void* stream) {
-    enter(e);
-    if (!e || !rows || !max_new || !seq_lens || !sampling) return fail(e, -22, "sr_admit_sampling: null argument");
-    const int total = check_fanout(e, "sr_admit_sampling", seq_lens, fanout, rows, n, e->c.max_batch, "row", max_new);
-    if (total < 0) return total;
-    if (int rc = check_sampling(e, "sr_admit_sampling", sampling, total)) return rc;
-    SR_TRY(ensure_row_params(e, (hipStream_t)stream));
-    int32_t first[MAXB];
-    first_forks(fanout, rows, n, first);
-    return prefill_impl(e, ids, pos3, seq_lens, first, n, image_embeds, n_image_rows, logits_out, stream, max_new, nullptr, true, fanout, rows,
-                        sampling);
+    if (!sampling) return fail(e, -22, "sr_admit_sampling: null argument");
+    return admit(e, "sr_admit_sampling", TO_ROWS, Prompts{ids, pos3, seq_lens, n, image_embeds, n_image_rows, logits_out, stream}, fanout, rows, max_new, sampling);
 }
 
 int sr_admit_commit(sr_engine* e, const int32_t* rows, int n, void* stream) {
@@ -1463,25 +1634,6 @@ int sr_admit_commit(sr_engine* e, const int32_t* rows, int n, void* stream) {
             if (rows[i] == rows[j]) return fail(e, -22, "sr_admit_commit: row %d given twice", rows[i]);
     }
     return commit_admission(e, rows, n, (hipStream_t)stream);
-}
-
-// one decode step (bookkeeping kernel + forward) captured once per (B, eos count, pad) and replayed
-static int ensure_decode_graph(sr_engine* e, int B, int n_eos, int pad_id) {
-    const int m = e->px_mode;
-    if (e->graph[m] != nullptr && e->graph_B[m] == B && e->graph_neos[m] == n_eos && e->graph_pad[m] == pad_id) return 0;
-    if (e->graph[m]) { (void)hipGraphExecDestroy(e->graph[m]); e->graph[m] = nullptr; }
-    hipGraph_t g = nullptr;
-    SR_TRY((int)hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
-    int rc = enqueue_step(e, B, n_eos, pad_id, nullptr, e->cap_stream);
-    if (!rc) rc = enqueue_decode_forward(e, B, e->cap_stream);
-    hipError_t er = hipStreamEndCapture(e->cap_stream, &g);
-    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-    SR_TRY((int)er);
-    er = hipGraphInstantiate(&e->graph[m], g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    SR_TRY((int)er);
-    e->graph_B[m] = B; e->graph_neos[m] = n_eos; e->graph_pad[m] = pad_id;
-    return 0;
 }
 
 int sr_decode(sr_engine* e, const int32_t* host_slots, int B, int max_new, const int32_t* host_eos, int n_eos, int32_t pad_id,
@@ -1507,45 +1659,11 @@ int sr_decode(sr_engine* e, const int32_t* host_slots, int B, int max_new, const
         if (max_new != c.max_new_tokens) return fail(e, -22, "teacher forcing requires max_new == max_new_tokens (%d)", c.max_new_tokens);
         forced_dev = forced;
     }
-    const bool graph_ok = use_graph && !logits_trace && !forced;
-    if (graph_ok) if (int rc = ensure_decode_graph(e, B, n_eos, pad_id)) return rc;
-    int done = 0;
-    std::vector<int> fin(B);
-    for (int i = 0; i < max_new; ++i) {
-        if (i == max_new - 1) {   // the last token only needs to be recorded
-            if (int rc = enqueue_step(e, B, n_eos, pad_id, forced_dev, s)) return rc;
-            done = max_new;
-            break;
-        }
-        if (graph_ok) SR_TRY((int)hipGraphLaunch(e->graph[e->px_mode], s));
-        else {
-            if (int rc = enqueue_step(e, B, n_eos, pad_id, forced_dev, s)) return rc;
-            if (int rc = enqueue_decode_forward(e, B, s)) return rc;
-            if (logits_trace)
-                SR_TRY((int)hipMemcpyAsync(logits_trace + (size_t)(i + 1) * B * V, e->d_logits, B * V * 4, hipMemcpyDeviceToDevice, s));
-        }
-        done = i + 1;
-        if (n_eos && (i % 16) == 15) {   // early exit once every sequence has emitted an eos token
-            SR_TRY((int)hipMemcpyAsync(fin.data(), e->d_finished, B * 4, hipMemcpyDeviceToHost, s));
-            SR_TRY((int)hipStreamSynchronize(s));
-            bool all = true;
-            for (int b = 0; b < B; ++b) all &= fin[b] != 0;
-            if (all) break;
-        }
-    }
-    // token log [B][max_new_tokens] -> caller layout [B][max_new]; unwritten positions read as pad
-    if (done < max_new) {
-        // fill the tail of the device log with pad before copying out
-        std::vector<int> padrow(max_new, pad_id);
-        for (int b = 0; b < B; ++b)
-            SR_TRY((int)hipMemcpyAsync(e->d_tokens + (size_t)b * c.max_new_tokens + done, padrow.data(), (max_new - done) * 4, hipMemcpyHostToDevice, s));
-        SR_TRY((int)hipStreamSynchronize(s));
-    }
-    SR_TRY((int)hipMemcpy2DAsync(tokens_out, (size_t)max_new * 4, e->d_tokens, (size_t)c.max_new_tokens * 4, (size_t)max_new * 4, B,
-                                 hipMemcpyDeviceToDevice, s));
-    SR_TRY((int)hipStreamSynchronize(s));
-    if (steps_done) *steps_done = done;
-    return 0;
+    Step st = make_step(B, n_eos, pad_id, nullptr);      // bookkeeping kernel + forward: k_step reduces the LM head's arg-max partials itself
+    st.forced = forced_dev;
+    hipGraphExec_t exec = nullptr;
+    if (use_graph && !logits_trace && !forced) if (int rc = step_graph(e, STEP_GREEDY, st, &exec)) return rc;
+    return decode_static(e, st, exec, max_new, logits_trace ? logits_trace + B * V : nullptr, tokens_out, s, steps_done);
 }
 
 // Sampled decode (temperature / top-k / top-p / repetition penalty of vllm_strategy.py:289-309), entirely on the device:
@@ -1566,62 +1684,17 @@ int sr_decode_sample(sr_engine* e, int B, int max_new, const int32_t* host_eos, 
     hipStream_t s = (hipStream_t)stream;
     if (n_eos) SR_TRY((int)hipMemcpyAsync(e->d_eos, host_eos, n_eos * 4, hipMemcpyHostToDevice, s));
     const bool rp = rep_penalty != 1.0f;
-    const float it = 1.0f / temperature;
-    const int hn = fused_norms(e, B) ? 1 : 0;
-    SampleArgs sa{e->d_logits, c.t_vocab, B, it, top_k, top_p, rep_penalty, rp ? e->d_seen : nullptr, e->seen_words, seed, e->d_step, e->d_sampled,
-                  e->d_amax_val, gemv_f32_blocks(c.t_vocab, B, c.t_hidden, hn), gemv_f32_block_rows(c.t_vocab, B, c.t_hidden, hn)};
+    Step st = make_step(B, n_eos, pad_id, e->d_sampled);      // one step: consume the drawn token, forward, draw the next
+    st.mark = rp ? Step::MARK_CHOSEN : Step::MARK_NONE;
+    st.tail = Step::TAIL_SAMPLE;
+    st.sample = sample_args(e, B, false);
+    st.sample.inv_temp = 1.0f / temperature; st.sample.top_k = top_k; st.sample.top_p = top_p; st.sample.rep_penalty = rep_penalty;
+    st.sample.seen = rp ? e->d_seen : nullptr; st.sample.seed = seed;
     if (rp) SR_TRY(launch_mark_prompt(s, e->t_src, e->t_lastrow, e->d_seen, e->seen_words, B));
-    SR_TRY(launch_sample(s, sa));                  // first token, from the prefill logits
-    auto enqueue = [&](hipStream_t q) -> int {     // one step: consume the drawn token, forward, draw the next
-        if (int rc = enqueue_step(e, B, n_eos, pad_id, nullptr, q, e->d_sampled)) return rc;
-        if (rp) SR_TRY(launch_mark_chosen(q, e->d_sampled, e->d_seen, e->seen_words, B));
-        if (int rc = enqueue_decode_forward(e, B, q)) return rc;
-        return launch_sample(q, sa);
-    };
-    if (use_graph && (e->sgraph == nullptr || e->sg_B != B || e->sg_neos != n_eos || e->sg_pad != pad_id || e->sg_topk != top_k ||
-                      e->sg_it != it || e->sg_topp != top_p || e->sg_rp != rep_penalty || e->sg_seed != seed || e->sg_px != e->px_mode)) {
-        if (e->sgraph) { (void)hipGraphExecDestroy(e->sgraph); e->sgraph = nullptr; }
-        hipGraph_t g = nullptr;
-        SR_TRY((int)hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
-        int rc = enqueue(e->cap_stream);
-        hipError_t er = hipStreamEndCapture(e->cap_stream, &g);
-        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-        SR_TRY((int)er);
-        er = hipGraphInstantiate(&e->sgraph, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        SR_TRY((int)er);
-        e->sg_B = B; e->sg_neos = n_eos; e->sg_pad = pad_id; e->sg_topk = top_k; e->sg_it = it; e->sg_topp = top_p; e->sg_rp = rep_penalty; e->sg_seed = seed; e->sg_px = e->px_mode;
-    }
-    int done = 0;
-    std::vector<int> fin(B);
-    for (int i = 0; i < max_new; ++i) {
-        if (i == max_new - 1) {                    // the last token only needs to be recorded
-            if (int rc = enqueue_step(e, B, n_eos, pad_id, nullptr, s, e->d_sampled)) return rc;
-            done = max_new;
-            break;
-        }
-        if (use_graph) SR_TRY((int)hipGraphLaunch(e->sgraph, s));
-        else if (int rc = enqueue(s)) return rc;
-        done = i + 1;
-        if (n_eos && (i % 16) == 15) {
-            SR_TRY((int)hipMemcpyAsync(fin.data(), e->d_finished, B * 4, hipMemcpyDeviceToHost, s));
-            SR_TRY((int)hipStreamSynchronize(s));
-            bool all = true;
-            for (int b = 0; b < B; ++b) all &= fin[b] != 0;
-            if (all) break;
-        }
-    }
-    if (done < max_new) {
-        std::vector<int> padrow(max_new, pad_id);
-        for (int b = 0; b < B; ++b)
-            SR_TRY((int)hipMemcpyAsync(e->d_tokens + (size_t)b * c.max_new_tokens + done, padrow.data(), (max_new - done) * 4, hipMemcpyHostToDevice, s));
-        SR_TRY((int)hipStreamSynchronize(s));
-    }
-    SR_TRY((int)hipMemcpy2DAsync(tokens_out, (size_t)max_new * 4, e->d_tokens, (size_t)c.max_new_tokens * 4, (size_t)max_new * 4, B,
-                                 hipMemcpyDeviceToDevice, s));
-    SR_TRY((int)hipStreamSynchronize(s));
-    if (steps_done) *steps_done = done;
-    return 0;
+    if (int rc = enqueue_step_tail(e, st, s)) return rc;      // first token, from the prefill logits
+    hipGraphExec_t exec = nullptr;
+    if (use_graph) if (int rc = step_graph(e, STEP_SAMPLED, st, &exec)) return rc;
+    return decode_static(e, st, exec, max_new, nullptr, tokens_out, s, steps_done);
 }
 
 // Beam search (HF _beam_search, do_sample=False, early_stopping=False) over the G prompts of the last sr_prefill, W beams each, entirely on
@@ -1722,54 +1795,15 @@ int sr_decode_beam(sr_engine* e, int G, int W, int R, int max_new, const int32_t
                 e->bm_done, e->bm_stop, e->bm_eos, n_eos, pad_id, max_new, length_penalty, e->d_step, 0, e->d_slots, e->d_ctx_len, e->bm_plen,
                 e->bm_copies};
     KvSuffixArgs ka{e->kcache, e->vtcache, (long long)e->kv_layer_elems, c.t_layers, c.t_kv_heads, c.max_ctx, e->bm_copies, B, suffix_nx(max_new)};
-    auto select = [&](hipStream_t q) -> int {
-        SR_TRY(launch_beam_rowstats(q, ba));
-        SR_TRY(launch_beam_select(q, ba));
-        SR_TRY(launch_kv_suffix(q, ka));
-        return 0;
-    };
-    auto enqueue = [&](hipStream_t q) -> int {     // one step: feed the chosen tokens, forward, select the next ones
-        if (int rc = enqueue_step(e, B, 0, pad_id, nullptr, q, e->bm_tok)) return rc;
-        if (int rc = enqueue_decode_forward(e, B, q)) return rc;
-        return select(q);
-    };
-    const bool graph_ok = use_graph && !logits_trace;
-    if (graph_ok && (e->bgraph == nullptr || e->bg_B != B || e->bg_W != W || e->bg_K != K || e->bg_neos != n_eos || e->bg_pad != pad_id ||
-                     e->bg_max_new != max_new || e->bg_lp != length_penalty || e->bg_px != e->px_mode)) {
-        if (e->bgraph) { (void)hipGraphExecDestroy(e->bgraph); e->bgraph = nullptr; }
-        hipGraph_t g = nullptr;
-        SR_TRY((int)hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
-        int rc = enqueue(e->cap_stream);
-        hipError_t er = hipStreamEndCapture(e->cap_stream, &g);
-        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-        SR_TRY((int)er);
-        er = hipGraphInstantiate(&e->bgraph, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        SR_TRY((int)er);
-        e->bg_B = B; e->bg_W = W; e->bg_K = K; e->bg_neos = n_eos; e->bg_pad = pad_id; e->bg_max_new = max_new; e->bg_lp = length_penalty;
-        e->bg_px = e->px_mode;
-    }
+    Step step = make_step(B, 0, pad_id, e->bm_tok);      // one step: feed the chosen tokens, forward, select the next ones
+    step.tail = Step::TAIL_BEAM; step.beam = &ba; step.suffix = &ka;
+    hipGraphExec_t exec = nullptr;
+    if (use_graph && !logits_trace) if (int rc = step_graph(e, STEP_BEAM, step, &exec)) return rc;
     if (logits_trace) SR_TRY((int)hipMemcpyAsync(logits_trace, e->d_logits, B * V * 4, hipMemcpyDeviceToDevice, s));
-    if (int rc = select(s)) return rc;             // step 0, from the prompts' logits
+    if (int rc = enqueue_step_tail(e, step, s)) return rc;      // step 0, from the prompts' logits
+    // steps 1 .. max_new - 1 (every one selects: none only records), with an early exit once every group has stopped
     int done = 1;
-    std::vector<int> gd(G);
-    for (int i = 1; i < max_new; ++i) {
-        if (graph_ok) SR_TRY((int)hipGraphLaunch(e->bgraph, s));
-        else {
-            if (int rc = enqueue_step(e, B, 0, pad_id, nullptr, s, e->bm_tok)) return rc;
-            if (int rc = enqueue_decode_forward(e, B, s)) return rc;
-            if (logits_trace) SR_TRY((int)hipMemcpyAsync(logits_trace + (size_t)i * B * V, e->d_logits, B * V * 4, hipMemcpyDeviceToDevice, s));
-            if (int rc = select(s)) return rc;
-        }
-        done = i + 1;
-        if ((i % 16) == 15) {                      // early exit once every group has stopped
-            SR_TRY((int)hipMemcpyAsync(gd.data(), e->bm_done, G * 4, hipMemcpyDeviceToHost, s));
-            SR_TRY((int)hipStreamSynchronize(s));
-            bool all = true;
-            for (int g = 0; g < G; ++g) all &= gd[g] != 0;
-            if (all) break;
-        }
-    }
+    if (int rc = run_steps(e, step, exec, 1, max_new, false, logits_trace ? logits_trace + B * V : nullptr, e->bm_done, G, s, &done)) return rc;
     // ---- the finished lists and the trace -> host; backtrack the R best hypotheses of every group
     std::vector<BeamFin> fin(B);
     std::vector<int> fin_n(G);
@@ -1808,60 +1842,21 @@ int sr_rows_step(sr_engine* e, int n_steps, const int32_t* host_eos, int n_eos, 
     hipStream_t s = (hipStream_t)stream;
     if (n_eos) SR_TRY((int)hipMemcpyAsync(e->d_eos, host_eos, n_eos * 4, hipMemcpyHostToDevice, s));
     const int B = e->c.max_batch;
+    const bool sampled = e->rows_perrow || e->rows_temp > 0.f;
+    Step st = make_step(B, n_eos, pad_id, sampled ? e->d_sampled : nullptr);
+    StepKind kind = STEP_GREEDY;
+    if (sampled) { st.tail = Step::TAIL_SAMPLE; st.sample = sample_args(e, B, false); }
     if (e->rows_perrow) {          // per-row step: mark the consumed tokens, consume them, forward, draw every row under its own table entry
-        const sr_config& c = e->c;
-        auto& pg = e->pgraph[e->px_mode];
-        if (pg.g == nullptr || pg.neos != n_eos || pg.pad != pad_id) {
-            if (pg.g) { (void)hipGraphExecDestroy(pg.g); pg.g = nullptr; }
-            const int hn = fused_norms(e, B) ? 1 : 0;
-            SampleArgs sa{e->d_logits, c.t_vocab, B, 1.0f, 1, 1.0f, 1.0f, e->rp_seen, e->seen_words, 0u, e->d_step, e->d_sampled,
-                          e->d_amax_val, gemv_f32_blocks(c.t_vocab, B, c.t_hidden, hn), gemv_f32_block_rows(c.t_vocab, B, c.t_hidden, hn)};
-            sa.params = e->rp_rows;
-            sa.seen_slot = e->d_slots;
-            hipGraph_t g = nullptr;
-            SR_TRY((int)hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
-            int rc = launch_mark_rows(e->cap_stream, e->d_sampled, e->d_finished, e->d_slots, e->rp_seen, e->seen_words, B);
-            if (!rc) rc = enqueue_step(e, B, n_eos, pad_id, nullptr, e->cap_stream, e->d_sampled);
-            if (!rc) rc = enqueue_decode_forward(e, B, e->cap_stream);
-            if (!rc) rc = launch_sample(e->cap_stream, sa);
-            hipError_t er = hipStreamEndCapture(e->cap_stream, &g);
-            if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-            SR_TRY((int)er);
-            er = hipGraphInstantiate(&pg.g, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            SR_TRY((int)er);
-            pg.neos = n_eos; pg.pad = pad_id;
-        }
-        for (int i = 0; i < n_steps; ++i) SR_TRY((int)hipGraphLaunch(pg.g, s));
-        return 0;
+        kind = STEP_ROWS_PERROW;
+        st.mark = Step::MARK_ROWS;
+        st.sample.seen = e->rp_seen; st.sample.params = e->rp_rows; st.sample.seen_slot = e->d_slots;
+    } else if (sampled) {          // sampled step: consume the drawn tokens, forward, draw the next ones for every row
+        kind = STEP_ROWS_SAMPLED;
+        st.sample.inv_temp = 1.0f / e->rows_temp; st.sample.top_k = e->rows_topk; st.sample.top_p = e->rows_topp; st.sample.seed = e->rows_seed;
     }
-    if (e->rows_temp > 0.f) {      // sampled step: consume the drawn tokens, forward, draw the next ones for every row
-        const sr_config& c = e->c;
-        const float it = 1.0f / e->rows_temp;
-        auto& rg = e->rgraph[e->px_mode];
-        if (rg.g == nullptr || rg.neos != n_eos || rg.pad != pad_id || rg.topk != e->rows_topk || rg.it != it || rg.topp != e->rows_topp || rg.seed != e->rows_seed) {
-            if (rg.g) { (void)hipGraphExecDestroy(rg.g); rg.g = nullptr; }
-            const int hn = fused_norms(e, B) ? 1 : 0;
-            SampleArgs sa{e->d_logits, c.t_vocab, B, it, e->rows_topk, e->rows_topp, 1.0f, nullptr, e->seen_words, e->rows_seed, e->d_step, e->d_sampled,
-                          e->d_amax_val, gemv_f32_blocks(c.t_vocab, B, c.t_hidden, hn), gemv_f32_block_rows(c.t_vocab, B, c.t_hidden, hn)};
-            hipGraph_t g = nullptr;
-            SR_TRY((int)hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
-            int rc = enqueue_step(e, B, n_eos, pad_id, nullptr, e->cap_stream, e->d_sampled);
-            if (!rc) rc = enqueue_decode_forward(e, B, e->cap_stream);
-            if (!rc) rc = launch_sample(e->cap_stream, sa);
-            hipError_t er = hipStreamEndCapture(e->cap_stream, &g);
-            if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-            SR_TRY((int)er);
-            er = hipGraphInstantiate(&rg.g, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            SR_TRY((int)er);
-            rg.neos = n_eos; rg.pad = pad_id; rg.topk = e->rows_topk; rg.it = it; rg.topp = e->rows_topp; rg.seed = e->rows_seed;
-        }
-        for (int i = 0; i < n_steps; ++i) SR_TRY((int)hipGraphLaunch(rg.g, s));
-        return 0;
-    }
-    if (int rc = ensure_decode_graph(e, B, n_eos, pad_id)) return rc;
-    for (int i = 0; i < n_steps; ++i) SR_TRY((int)hipGraphLaunch(e->graph[e->px_mode], s));
+    hipGraphExec_t exec = nullptr;
+    if (int rc = step_graph(e, kind, st, &exec)) return rc;
+    for (int i = 0; i < n_steps; ++i) SR_TRY((int)hipGraphLaunch(exec, s));
     return 0;
 }
 
@@ -1915,25 +1910,12 @@ int sr_decode_step(sr_engine* e, const int64_t* dev_last_ids, int B, float* dev_
     hipStream_t s = (hipStream_t)stream;
     // eos handling stays with the caller (n_eos = 0): a finished row is simply ignored by whoever samples.
     // One captured graph per (token source, B): step bookkeeping + forward + greedy ids, replayed from engine-owned buffers.
-    const int kind = dev_last_ids ? 1 : 0;
-    const int n_part = gemv_f32_blocks(c.t_vocab, B, c.t_hidden, fused_norms(e, B) ? 1 : 0);
-    if (e->step_graph[kind] == nullptr || e->step_graph_B[kind] != B || e->step_graph_px[kind] != e->px_mode) {
-        if (e->step_graph[kind]) { (void)hipGraphExecDestroy(e->step_graph[kind]); e->step_graph[kind] = nullptr; }
-        hipGraph_t g = nullptr;
-        SR_TRY((int)hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed));
-        int rc = enqueue_step(e, B, 0, 0, nullptr, e->cap_stream, kind ? e->d_chosen : nullptr);
-        if (!rc) rc = enqueue_decode_forward(e, B, e->cap_stream);
-        if (!rc) rc = launch_next_ids(e->cap_stream, e->d_amax_val, e->d_amax_idx, n_part, B, e->d_next);
-        hipError_t er = hipStreamEndCapture(e->cap_stream, &g);
-        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-        SR_TRY((int)er);
-        er = hipGraphInstantiate(&e->step_graph[kind], g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        SR_TRY((int)er);
-        e->step_graph_B[kind] = B; e->step_graph_px[kind] = e->px_mode;
-    }
-    if (kind) SR_TRY((int)hipMemcpyAsync(e->d_chosen, dev_last_ids, (size_t)B * 8, hipMemcpyDeviceToDevice, s));
-    SR_TRY((int)hipGraphLaunch(e->step_graph[kind], s));
+    Step st = make_step(B, 0, 0, dev_last_ids ? e->d_chosen : nullptr);
+    st.tail = Step::TAIL_NEXT_IDS;
+    hipGraphExec_t exec = nullptr;
+    if (int rc = step_graph(e, dev_last_ids ? STEP_CALLER_CHOSEN : STEP_CALLER_GREEDY, st, &exec)) return rc;
+    if (dev_last_ids) SR_TRY((int)hipMemcpyAsync(e->d_chosen, dev_last_ids, (size_t)B * 8, hipMemcpyDeviceToDevice, s));
+    SR_TRY((int)hipGraphLaunch(exec, s));
     if (dev_logits_out) SR_TRY((int)hipMemcpyAsync(dev_logits_out, e->d_logits, (size_t)B * c.t_vocab * 4, hipMemcpyDeviceToDevice, s));
     if (dev_next_ids) SR_TRY((int)hipMemcpyAsync(dev_next_ids, e->d_next, (size_t)B * 8, hipMemcpyDeviceToDevice, s));
     return 0;

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import Iterable, Sequence
 
 import numpy as np
@@ -176,22 +177,29 @@ class Engine:
                 slots: Iterable[int] | None = None, return_logits: bool = False):
         """ids[b]: int64 [S_b]; pos3[b]: int64 [3, S_b] (un-padded).  Fills KV slots, returns float32 logits [B, V] if asked."""
         B = len(ids)
-        lens = np.array([len(x) for x in ids], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
-        p3 = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int64).reshape(3, -1) for p in pos3], axis=1))
         sl = np.arange(B, dtype=np.int32) if slots is None else np.asarray(list(slots), dtype=np.int32)
-        logits = torch.empty(B, self.geom.text.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
-        n_img = 0 if image_embeds is None else int(image_embeds.shape[0])
-        if image_embeds is not None:
-            image_embeds = image_embeds.contiguous()
-            assert image_embeds.dtype == torch.bfloat16
-        L.check(self.lib.sr_prefill(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p),
-                                    lens.ctypes.data_as(L._i32p), sl.ctypes.data_as(L._i32p), B,
-                                    C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None, n_img,
-                                    C.c_void_p(logits.data_ptr()) if logits is not None else None, self._s()),
-                self._h, "sr_prefill")
+        pk = self._pack(ids, pos3, image_embeds, return_logits, B)
+        L.check(self.lib.sr_prefill(self._h, *pk.prompts, sl.ctypes.data_as(L._i32p), B, *pk.images, pk.logits_p, self._s()), self._h, "sr_prefill")
         self._last_B = B
-        return logits
+        return pk.logits
+
+    def _pack(self, ids, pos3, image_embeds, return_logits, n_logit_rows):
+        """The packed prompts as ctypes arguments, shared by prefill / forward_logits / admit / admit_stage: .prompts = (flattened ids,
+        concatenated pos3, lengths), .images = (bf16 image features or None, their row count), .logits / .logits_p = the optional float32
+        [n_logit_rows, V] output and its pointer.  The namespace keeps the arrays alive for the call."""
+        pk = SimpleNamespace()
+        pk.lens = np.array([len(x) for x in ids], dtype=np.int32)
+        pk.flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
+        pk.p3 = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int64).reshape(3, -1) for p in pos3], axis=1))
+        pk.prompts = (pk.flat.ctypes.data_as(L._i64p), pk.p3.ctypes.data_as(L._i64p), pk.lens.ctypes.data_as(L._i32p))
+        pk.emb = None
+        if image_embeds is not None:
+            pk.emb = image_embeds.contiguous()
+            assert pk.emb.dtype == torch.bfloat16
+        pk.images = (C.c_void_p(pk.emb.data_ptr()) if pk.emb is not None else None, 0 if pk.emb is None else int(pk.emb.shape[0]))
+        pk.logits = torch.empty(n_logit_rows, self.geom.text.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
+        pk.logits_p = C.c_void_p(pk.logits.data_ptr()) if pk.logits is not None else None
+        return pk
 
     def decode_sample(self, max_new: int, temperature: float, top_k: int, top_p: float = 1.0, repetition_penalty: float = 1.0,
                       seed: int = 0, eos: Sequence[int] = (), pad_id: int = 0, use_graph: bool = True) -> torch.Tensor:
@@ -234,18 +242,10 @@ class Engine:
     def forward_logits(self, ids: Sequence[np.ndarray], pos3: Sequence[np.ndarray], image_embeds: torch.Tensor | None = None):
         """Teacher-forced forward: float32 logits [n_tok, V] for every position of the packed sequences."""
         B = len(ids)
-        lens = np.array([len(x) for x in ids], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
-        p3 = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int64).reshape(3, -1) for p in pos3], axis=1))
-        out = torch.empty(len(flat), self.geom.text.vocab_size, dtype=torch.float32, device=self.device)
-        n_img = 0 if image_embeds is None else int(image_embeds.shape[0])
-        if image_embeds is not None:
-            image_embeds = image_embeds.contiguous()
-        L.check(self.lib.sr_forward_logits(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p), B,
-                                           C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None, n_img,
-                                           C.c_void_p(out.data_ptr()), self._s()), self._h, "sr_forward_logits")
+        pk = self._pack(ids, pos3, image_embeds, True, sum(len(x) for x in ids))
+        L.check(self.lib.sr_forward_logits(self._h, *pk.prompts, B, *pk.images, pk.logits_p, self._s()), self._h, "sr_forward_logits")
         self._last_B = B
-        return out
+        return pk.logits
 
     def decode(self, max_new: int, eos: Sequence[int] = (), pad_id: int = 0, trace: bool = False,
                forced: torch.Tensor | None = None, use_graph: bool = True):
@@ -288,58 +288,34 @@ class Engine:
         sequence, prompt-major, and max_new stays per prompt.  The logits (return_logits) have one row per prompt.
         sampling: one (temperature, top_k, top_p, repetition_penalty, seed, stream) per SEQUENCE (sr_admit_sampling; temperature 0 = greedy,
         stream < 0 = the row's stream of rows_sampling)."""
-        if sampling is not None:
-            return self._admit_sampling(False, rows, ids, pos3, max_new, image_embeds, return_logits, fanout, sampling)
-        n = len(ids)
-        lens = np.array([len(x) for x in ids], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
-        p3 = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int64).reshape(3, -1) for p in pos3], axis=1))
-        rw = np.asarray(list(rows), dtype=np.int32)
-        mn = np.asarray(list(max_new), dtype=np.int32)
-        logits = torch.empty(n, self.geom.text.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
-        n_img = 0 if image_embeds is None else int(image_embeds.shape[0])
-        if image_embeds is not None:
-            image_embeds = image_embeds.contiguous()
-            assert image_embeds.dtype == torch.bfloat16
-        emb_p = C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None
-        lg_p = C.c_void_p(logits.data_ptr()) if logits is not None else None
-        if fanout is None:
-            L.check(self.lib.sr_admit(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
-                                      rw.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n, emb_p, n_img, lg_p, self._s()), self._h, "sr_admit")
-        else:
-            fo = np.asarray(list(fanout), dtype=np.int32)
-            assert len(fo) == n and len(rw) == int(fo.sum()), "fanout: one entry per prompt, one row per forked sequence"
-            L.check(self.lib.sr_admit_fanout(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
-                                             fo.ctypes.data_as(L._i32p), rw.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n, emb_p, n_img,
-                                             lg_p, self._s()), self._h, "sr_admit_fanout")
-        return logits
+        return self._admit(False, rows, ids, pos3, max_new, image_embeds, return_logits, fanout, sampling)
 
     _SMP = np.dtype([("temperature", "<f4"), ("top_k", "<i4"), ("top_p", "<f4"), ("repetition_penalty", "<f4"), ("seed", "<u4"), ("stream", "<i4")])
 
-    def _admit_sampling(self, stage, dst, ids, pos3, max_new, image_embeds, return_logits, fanout, sampling):
-        """admit / admit_stage with one sr_sampling entry per sequence (sr_admit_sampling / sr_admit_stage_sampling)"""
+    def _admit(self, stage, dst, ids, pos3, max_new, image_embeds, return_logits, fanout, sampling):
+        """admit / admit_stage: dst = rows / KV slots.  Calls the plain entry point, its _fanout form (fanout given) or its _sampling form
+        (one sr_sampling entry per sequence): the first use of a _sampling entry allocates the library's per-row table, so the general
+        form is not used for the simpler requests"""
         n = len(ids)
-        lens = np.array([len(x) for x in ids], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
-        p3 = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int64).reshape(3, -1) for p in pos3], axis=1))
+        what = "KV slot" if stage else "row"
+        pk = self._pack(ids, pos3, image_embeds, return_logits, n)
         d = np.asarray(list(dst), dtype=np.int32)
         mn = np.asarray(list(max_new), dtype=np.int32)
         fo = None if fanout is None else np.asarray(list(fanout), dtype=np.int32)
-        assert len(d) == (n if fo is None else int(fo.sum())), "one row / KV slot per sequence"
-        smp = np.array([(float(t), int(k), float(p), float(rp), int(s) & 0xffffffff, int(st)) for t, k, p, rp, s, st in sampling], dtype=self._SMP)
-        assert len(smp) == len(d), "one sampling entry per sequence"
-        n_img = 0 if image_embeds is None else int(image_embeds.shape[0])
-        if image_embeds is not None:
-            image_embeds = image_embeds.contiguous()
-            assert image_embeds.dtype == torch.bfloat16
-        logits = torch.empty(n, self.geom.text.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
-        fn = self.lib.sr_admit_stage_sampling if stage else self.lib.sr_admit_sampling
-        L.check(fn(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
-                   fo.ctypes.data_as(L._i32p) if fo is not None else None, d.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p),
-                   C.c_void_p(smp.ctypes.data), n, C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None, n_img,
-                   C.c_void_p(logits.data_ptr()) if logits is not None else None, self._s()),
-                self._h, "sr_admit_stage_sampling" if stage else "sr_admit_sampling")
-        return logits
+        assert fo is None or (len(fo) == n and len(d) == int(fo.sum())), f"fanout: one entry per prompt, one {what} per forked sequence"
+        name = "sr_admit_stage" if stage else "sr_admit"
+        args = [d.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p)]
+        if sampling is not None:
+            assert fo is not None or len(d) == n, f"one {what} per sequence"
+            smp = np.array([(float(t), int(k), float(p), float(rp), int(s) & 0xffffffff, int(st)) for t, k, p, rp, s, st in sampling], dtype=self._SMP)
+            assert len(smp) == len(d), "one sampling entry per sequence"
+            name += "_sampling"
+            args = [fo.ctypes.data_as(L._i32p) if fo is not None else None] + args + [C.c_void_p(smp.ctypes.data)]
+        elif fo is not None:
+            name += "_fanout"
+            args = [fo.ctypes.data_as(L._i32p)] + args
+        L.check(getattr(self.lib, name)(self._h, *pk.prompts, *args, n, *pk.images, pk.logits_p, self._s()), self._h, name)
+        return pk.logits
 
     def admit_stage(self, kv_slots: Sequence[int], ids: Sequence[np.ndarray], pos3: Sequence[np.ndarray], max_new: Sequence[int],
                     image_embeds: torch.Tensor | None = None, fanout: Sequence[int] | None = None, return_logits: bool = False,
@@ -347,32 +323,7 @@ class Engine:
         """First half of an admission, on the CURRENT torch stream (normally a CU-masked side stream): prefill into spare KV slots, LM
         head, first token.  No row state is touched; admit_commit installs the sequences into rows later.  fanout: as admit (kv_slots then
         has one slot per forked sequence, prompt-major); sampling: as admit."""
-        if sampling is not None:
-            return self._admit_sampling(True, kv_slots, ids, pos3, max_new, image_embeds, return_logits, fanout, sampling)
-        n = len(ids)
-        lens = np.array([len(x) for x in ids], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64) for x in ids]))
-        p3 = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int64).reshape(3, -1) for p in pos3], axis=1))
-        sl = np.asarray(list(kv_slots), dtype=np.int32)
-        mn = np.asarray(list(max_new), dtype=np.int32)
-        n_img = 0 if image_embeds is None else int(image_embeds.shape[0])
-        if image_embeds is not None:
-            image_embeds = image_embeds.contiguous()
-            assert image_embeds.dtype == torch.bfloat16
-        emb_p = C.c_void_p(image_embeds.data_ptr()) if image_embeds is not None else None
-        logits = torch.empty(n, self.geom.text.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
-        lg_p = C.c_void_p(logits.data_ptr()) if logits is not None else None
-        if fanout is None:
-            L.check(self.lib.sr_admit_stage(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
-                                            sl.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n, emb_p, n_img, lg_p, self._s()),
-                    self._h, "sr_admit_stage")
-        else:
-            fo = np.asarray(list(fanout), dtype=np.int32)
-            assert len(fo) == n and len(sl) == int(fo.sum()), "fanout: one entry per prompt, one KV slot per forked sequence"
-            L.check(self.lib.sr_admit_stage_fanout(self._h, flat.ctypes.data_as(L._i64p), p3.ctypes.data_as(L._i64p), lens.ctypes.data_as(L._i32p),
-                                                   fo.ctypes.data_as(L._i32p), sl.ctypes.data_as(L._i32p), mn.ctypes.data_as(L._i32p), n, emb_p,
-                                                   n_img, lg_p, self._s()), self._h, "sr_admit_stage_fanout")
-        return logits
+        return self._admit(True, kv_slots, ids, pos3, max_new, image_embeds, return_logits, fanout, sampling)
 
     def admit_commit(self, rows: Sequence[int]):
         """Second half, on the decode stream between two steps: batch row rows[i] takes over the i-th staged sequence (and its KV slot)."""
