@@ -282,6 +282,22 @@ int sr_render_overlay(uint8_t* dev_img_rgb, int h, int w, const uint8_t* dev_mas
  *   sr_op_attention : softmax(q k^T * scale) v per work item (struct {int q_row0, seq_len, q_off, k_row0; int64 vt_off; int q_len, pad}
  *                     on the device, one item per q_tile queries of a sequence / window); V is passed TRANSPOSED ([head*hd + d][key]).
  *                     head_dim 16 / 32 / 80 / 128 (72 runs as 80 with zero channels).  v2_ok: vt key runs are 16-byte aligned and finite.
+ *                     Preconditions (the kernels check none of them; tests/attention_ref.py check_preconditions is their executable form):
+ *                       - q_stride, k_stride, k_head_stride and head_dim are multiples of 8 elements and q / k 16-byte aligned (16-byte
+ *                         fragment loads); vt 8-byte aligned, vt_stride, vt_head_stride and every vt_off multiples of 4 elements, and each
+ *                         V^T key run readable up to the next multiple of 4 keys past seq_len (8-byte loads; what lies past seq_len is
+ *                         masked, it may be other data, NaN or inf); out 8-byte aligned and out_stride a multiple of 4.  K rows past
+ *                         seq_len are never read (row indices are clamped to seq_len - 1).
+ *                       - an item covers queries q_off .. min(q_off + q_tile, q_len ? q_len : seq_len) of its sequence (q_off a multiple
+ *                         of q_tile, seq_len >= 1) and writes exactly those rows, columns [0, n_heads * head_dim); kv head = head / group.
+ *                       - q_tile 0 / 64: head_dim 128 (causal or not), 80 / 32 / 16 (not causal).  q_tile 16: head_dim 16, not causal
+ *                         (<= 16 queries per item, the block's waves split the keys).  Anything else returns -22 before a launch;
+ *                         n_work 0 returns 0.
+ *                       - v2_ok = 1 additionally promises: vt 16-byte aligned, vt_off, vt_stride and vt_head_stride multiples of 8; every
+ *                         V^T row allocated and FINITE up to the end of the last 64-key tile of its run (those values are multiplied by
+ *                         P = 0, not masked); items cut at q_tile queries.  It is used when n_heads % 4 == 0 and (head_dim 128, causal,
+ *                         q_tile 64, group % 4 == 0) or (head_dim 80, not causal, q_tile 128, group 1), with bit-identical results;
+ *                         q_tile 128 without it is refused.
  *   sr_op_sam_preprocess : uint8 HWC -> bf16 CHW [3][S][S], /255, bilinear resize, ImageNet normalisation.
  *   sr_op_im2col    : k x k / stride / pad windows of a CHW image -> GEMM operand rows (optional destination row map).
  *   sr_op_layernorm : LayerNorm with bias over C channels, pad columns [C, ldo) zeroed.
