@@ -52,6 +52,77 @@ __device__ __forceinline__ u32x4 ldg_nt(const bf16_t* p) {
 }
 __device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 
+// ---------------------------------------------------------------- epilogue pieces shared by both tile families
+// SwiGLU of 4 consecutive output columns (gate sums gt, up sums up) of batch row m, row-major or fragment-ordered (out_tiled)
+__device__ __forceinline__ void store_swiglu(const GemvArgs& p, int m, int col, const float (&gt)[4], const float (&up)[4]) {
+    float o[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float g = rbf(gt[r]), u = rbf(up[r]);
+        o[r] = rbf(silu_f(g)) * u;
+    }
+    bf16_t* ob = reinterpret_cast<bf16_t*>(p.out);
+    *reinterpret_cast<uint2*>(ob + (p.out_tiled ? tiled_offset((size_t)m, (size_t)col, (size_t)(p.N / 2))
+                                                : (size_t)m * (p.N / 2) + col)) = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
+}
+// fused greedy argmax, block part: every wave has left its (max, lowest index) per batch row in av / ai [WAVES][rows]; thread m < M combines them
+// (lowest index among equal maxima) into amax[m * stride + col]
+template <int WAVES>
+__device__ __forceinline__ void amax_combine(const GemvArgs& p, const float* av, const int* ai, int rows, int tid, int stride, int col) {
+    __syncthreads();
+    if (tid < p.M) {
+        float bv = av[tid];
+        int bi = ai[tid];
+        for (int w = 1; w < WAVES; ++w) {
+            const float ov = av[w * rows + tid];
+            const int oi = ai[w * rows + tid];
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        p.amax_val[(size_t)tid * stride + col] = bv;
+        p.amax_idx[(size_t)tid * stride + col] = bi;
+    }
+}
+
+// ---------------------------------------------------------------- 16-row-tile epilogue pieces (f32x4 acc[T][MT]: k_gemv, k_gemv_px)
+// in-block K reduction, fixed order kp = 1, 2, 3, through rb = this tile's [KP - 1][T * MT][64] quads
+template <int T, int MT, int KP>
+__device__ __forceinline__ void kreduce16(f32x4* rb, int kp, int lane, f32x4 (&acc)[T][MT]) {
+    if (kp > 0) {
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) rb[((kp - 1) * (T * MT) + t * MT + mt) * 64 + lane] = acc[t][mt];
+    }
+    __syncthreads();
+    if (kp == 0) {
+#pragma unroll
+        for (int k = 1; k < KP; ++k)
+#pragma unroll
+            for (int t = 0; t < T; ++t)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const f32x4 o = rb[((k - 1) * (T * MT) + t * MT + mt) * 64 + lane];
+                    acc[t][mt][0] += o[0]; acc[t][mt][1] += o[1]; acc[t][mt][2] += o[2]; acc[t][mt][3] += o[3];
+                }
+    }
+}
+// per-output-channel scale of the fp8 weights (engine row order, gate / up interleaved)
+template <int T, int MT>
+__device__ __forceinline__ void scale16(const GemvArgs& p, int tile, int fg, f32x4 (&acc)[T][MT]) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const float4 sc = *reinterpret_cast<const float4*>(p.w_scale + (size_t)(tile * T + t) * 16 + fg * 4);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            acc[t][mt][0] *= sc.x; acc[t][mt][1] *= sc.y; acc[t][mt][2] *= sc.z; acc[t][mt][3] *= sc.w;
+        }
+    }
+}
+// SwiGLU store of batch row m: the lane's 4 columns of gate tile 2 * tile and up tile 2 * tile + 1
+__device__ __forceinline__ void store_swiglu16(const GemvArgs& p, int tile, int m, int fg, const f32x4& gt, const f32x4& up) {
+    store_swiglu(p, m, tile * 16 + fg * 4, {gt[0], gt[1], gt[2], gt[3]}, {up[0], up[1], up[2], up[3]});
+}
+
 // WAVES = 4 : the dispatched configuration -- many small blocks, K split over the 4 waves.
 // STAGE     : x (optionally + pending residual slabs, optionally RMS-normalised) is prepared in LDS by the prologue
 //             (used for batches <= 4, where the prologue is a few KB per block).
@@ -388,40 +459,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs p, int ntiles) {
     f32x4* rbuf = reinterpret_cast<f32x4*>(STAGE ? smem : reinterpret_cast<unsigned char*>(red + 128));   // [TPB][KP-1][T*MT][64]
     if constexpr (KP > 1) {
         if constexpr (STAGE) __syncthreads();
-        if (kp > 0) {
-#pragma unroll
-            for (int t = 0; t < T; ++t)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-                    rbuf[((tp * (KP - 1) + (kp - 1)) * (T * MT) + t * MT + mt) * 64 + lane] = acc[t][mt];
-        }
-        __syncthreads();
-        if (kp == 0) {
-#pragma unroll
-            for (int k = 1; k < KP; ++k)
-#pragma unroll
-                for (int t = 0; t < T; ++t)
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        f32x4 o = rbuf[((tp * (KP - 1) + (k - 1)) * (T * MT) + t * MT + mt) * 64 + lane];
-                        acc[t][mt][0] += o[0]; acc[t][mt][1] += o[1]; acc[t][mt][2] += o[2]; acc[t][mt][3] += o[3];
-                    }
-        }
+        kreduce16<T, MT, KP>(rbuf + (size_t)tp * (KP - 1) * (T * MT) * 64, kp, lane, acc);
     }
 
     // ---------------------------------------------------------------- epilogue (wave kp == 0 of each tile)
     // lane owns batch row m = mt*16 + fr and output columns tile*16 + fg*4 + {0..3}
     if constexpr (F8) {
-        if (active && kp == 0) {        // per-output-channel scale of the fp8 weights (engine row order, gate / up interleaved)
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const float4 sc = *reinterpret_cast<const float4*>(p.w_scale + (size_t)(tile * T + t) * 16 + fg * 4);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) {
-                    acc[t][mt][0] *= sc.x; acc[t][mt][1] *= sc.y; acc[t][mt][2] *= sc.z; acc[t][mt][3] *= sc.w;
-                }
-            }
-        }
+        if (active && kp == 0) scale16<T, MT>(p, tile, fg, acc);
     }
     float bestv[MT];
     int besti[MT];
@@ -433,16 +477,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs p, int ntiles) {
             const int m = mt * 16 + fr;
             if (m >= p.M) continue;
             if constexpr (MODE == GV_SWIGLU) {
-                float o[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float g = rbf(acc[0][mt][r]), u = rbf(acc[1][mt][r]);
-                    o[r] = rbf(silu_f(g)) * u;
-                }
-                uint2 v = {pack2(o[0], o[1]), pack2(o[2], o[3])};
-                bf16_t* ob = reinterpret_cast<bf16_t*>(p.out);
-                *reinterpret_cast<uint2*>(ob + (p.out_tiled ? tiled_offset((size_t)m, (size_t)(tile * 16 + fg * 4), (size_t)(p.N / 2))
-                                                            : (size_t)m * (p.N / 2) + tile * 16 + fg * 4)) = v;
+                store_swiglu16(p, tile, m, fg, acc[0][mt], acc[T - 1][mt]);
             } else if constexpr (MODE == GV_BIAS || MODE == GV_RESID) {
                 const int n = tile * 16 + fg * 4;
                 bf16_t* optr = reinterpret_cast<bf16_t*>(p.out) + (size_t)m * p.ldo + n;
@@ -473,6 +508,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs p, int ntiles) {
     }
     if constexpr (MODE == GV_F32) {
         // fused greedy argmax: (max, lowest index) of this block's logits per batch row -> amax[m][blockIdx.x]
+        // (the wave part is this layout's own -- 4 lane groups per batch row, MT rows per lane, where amax32 folds 2 halves of 1 row; the block part is shared)
         if (p.amax_val) {
             if constexpr (STAGE) __syncthreads();      // KP == 1 here; the staged x is dead, reuse its region
             float* av = reinterpret_cast<float*>(rbuf);                 // [WAVES][32]
@@ -489,18 +525,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs p, int ntiles) {
                 }
                 if (fg == 0) { av[wave * 32 + mt * 16 + fr] = bv; ai[wave * 32 + mt * 16 + fr] = bi; }
             }
-            __syncthreads();
-            if (tid < p.M) {
-                float bv = av[tid];
-                int bi = ai[tid];
-                for (int w = 1; w < WAVES; ++w) {
-                    const float ov = av[w * 32 + tid];
-                    const int oi = ai[w * 32 + tid];
-                    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-                }
-                p.amax_val[(size_t)tid * gridDim.x + blockIdx.x] = bv;
-                p.amax_idx[(size_t)tid * gridDim.x + blockIdx.x] = bi;
-            }
+            amax_combine<WAVES>(p, av, ai, 32, tid, gridDim.x, blockIdx.x);
         }
     }
     TGV(3);
@@ -622,47 +647,13 @@ __global__ __launch_bounds__(256) void k_gemv_px(GemvArgs p, int ntiles) {
         else run_tile(F_{}, 0, acc);
         if (tid == 0) s_tile[(it + 2) & 3] = (int)ticket;
         // in-block K reduction, fixed order kp = 1, 2, 3 (k_gemv's); the buffer alternates so that a fast wave's partials of the next tile never meet a slow reader
-        f32x4* rb = rbuf + (size_t)(it & 1) * (KP - 1) * T * MT * 64;
-        if (kp > 0) {
-#pragma unroll
-            for (int t = 0; t < T; ++t)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) rb[((kp - 1) * (T * MT) + t * MT + mt) * 64 + lane] = acc[t][mt];
-        }
-        __syncthreads();
+        kreduce16<T, MT, KP>(rbuf + (size_t)(it & 1) * (KP - 1) * T * MT * 64, kp, lane, acc);
         if (kp == 0) {
-#pragma unroll
-            for (int k = 1; k < KP; ++k)
-#pragma unroll
-                for (int t = 0; t < T; ++t)
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        const f32x4 o = rb[((k - 1) * (T * MT) + t * MT + mt) * 64 + lane];
-                        acc[t][mt][0] += o[0]; acc[t][mt][1] += o[1]; acc[t][mt][2] += o[2]; acc[t][mt][3] += o[3];
-                    }
-            if constexpr (F8) {
-#pragma unroll
-                for (int t = 0; t < T; ++t) {
-                    const float4 sc = *reinterpret_cast<const float4*>(p.w_scale + (size_t)(tile * T + t) * 16 + fg * 4);
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        acc[t][mt][0] *= sc.x; acc[t][mt][1] *= sc.y; acc[t][mt][2] *= sc.z; acc[t][mt][3] *= sc.w;
-                    }
-                }
-            }
+            if constexpr (F8) scale16<T, MT>(p, tile, fg, acc);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const int m = mt * 16 + fr;
-                if (m >= p.M) continue;
-                float o[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float g = rbf(acc[0][mt][r]), u = rbf(acc[1][mt][r]);
-                    o[r] = rbf(silu_f(g)) * u;
-                }
-                bf16_t* ob = reinterpret_cast<bf16_t*>(p.out);
-                *reinterpret_cast<uint2*>(ob + (p.out_tiled ? tiled_offset((size_t)m, (size_t)(tile * 16 + fg * 4), (size_t)(p.N / 2))
-                                                            : (size_t)m * (p.N / 2) + tile * 16 + fg * 4)) = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
+                if (m < p.M) store_swiglu16(p, tile, m, fg, acc[0][mt], acc[1][mt]);
             }
         }
         tile = next;
@@ -702,6 +693,73 @@ __device__ __forceinline__ void rb_add(const unsigned char* smem, int slot, int 
         const float4 o = b[q * 64];
         a[4 * q] += o.x; a[4 * q + 1] += o.y; a[4 * q + 2] += o.z; a[4 * q + 3] += o.w;
     }
+}
+
+// ---------------------------------------------------------------- 32-row-tile epilogue (one f32x16 per 32 batch rows: k_gemv32, k_gemv32g, k_gemv32_px, k_gemv32_hpx)
+// lane = (batch row, half kg): acc[4 q + r] is weight row tile * 32 + 8 q + 4 kg + r -- four consecutive output columns per register quad q
+// register quad q of acc as the epilogue sees it; F8: times the per-output-channel scale of the fp8 weights (engine row order)
+template <bool F8>
+__device__ __forceinline__ void quad32(const GemvArgs& p, int tile, int kg, const f32x16& acc, int q, float (&o)[4]) {
+    o[0] = acc[q * 4]; o[1] = acc[q * 4 + 1]; o[2] = acc[q * 4 + 2]; o[3] = acc[q * 4 + 3];
+    if constexpr (F8) {
+        const float4 sc = *reinterpret_cast<const float4*>(p.w_scale + (size_t)tile * 32 + 8 * q + 4 * kg);
+        o[0] *= sc.x; o[1] *= sc.y; o[2] *= sc.z; o[3] *= sc.w;
+    }
+}
+// store of batch row m (PARTIAL: into float32 slab `slab`); F32 also keeps the lane's running (max, lowest index) in bestv / besti
+template <int MODE, bool F8>
+__device__ __forceinline__ void store32(const GemvArgs& p, int tile, int m, int kg, int slab, const f32x16& acc, float* bestv = nullptr, int* besti = nullptr) {
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+        const int nl = 8 * g4 + 4 * kg;                      // first of this quad's 4 consecutive weight rows
+        const int n = tile * 32 + 8 * g4 + 4 * kg;
+        float o[4];
+        quad32<F8>(p, tile, kg, acc, g4, o);
+        if constexpr (MODE == GV_SWIGLU) {                   // (gate / up interleave: rows r and r + 16 are gate and up of column tile * 16 + r)
+            if (g4 < 2) {
+                float up[4];
+                quad32<F8>(p, tile, kg, acc, g4 + 2, up);
+                store_swiglu(p, m, tile * 16 + nl, o, up);
+            }
+        } else if constexpr (MODE == GV_BIAS || MODE == GV_RESID) {
+            bf16_t* optr = reinterpret_cast<bf16_t*>(p.out) + (size_t)m * p.ldo + n;
+            if (MODE == GV_BIAS && p.bias) {
+                const uint2 b = *reinterpret_cast<const uint2*>(p.bias + n);
+                o[0] += lo16(b.x); o[1] += hi16(b.x); o[2] += lo16(b.y); o[3] += hi16(b.y);
+            }
+            if constexpr (MODE == GV_RESID) {
+                const uint2 rv = *reinterpret_cast<const uint2*>(optr);
+                o[0] = lo16(rv.x) + rbf(o[0]); o[1] = hi16(rv.x) + rbf(o[1]);
+                o[2] = lo16(rv.y) + rbf(o[2]); o[3] = hi16(rv.y) + rbf(o[3]);
+            }
+            *reinterpret_cast<uint2*>(optr) = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
+        } else {
+            // (n added term by term in 64 bits: the wave-uniform tile * 32 then stays in scalar registers through the persistent kernels' tile loops)
+            const size_t oi = ((size_t)(MODE == GV_PARTIAL ? slab : 0) * p.M + m) * p.N + tile * 32 + 8 * g4 + 4 * kg;
+            *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + oi) = float4{o[0], o[1], o[2], o[3]};
+            if constexpr (MODE == GV_F32) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (o[r] > *bestv || (o[r] == *bestv && n + r < *besti)) { *bestv = o[r]; *besti = n + r; }
+            }
+        }
+    }
+}
+// the block's argmax partial of a 4-wave F32 launch over G row groups: bestv / besti [G] of every lane (batch row `row` + 32 g, half kg) -> av = LDS
+// [4 waves][32 G] values + as many indices -> amax[m * stride + col].  No barrier behind the LDS reads: a caller that loops adds its own
+template <int G>
+__device__ __forceinline__ void amax32(const GemvArgs& p, float* av, const float* bestv, const int* besti, int row, int kg, int wave, int tid, int stride, int col) {
+    int* ai = reinterpret_cast<int*>(av + 4 * 32 * G);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        float bv = bestv[g];
+        int bi = besti[g];
+        const float ov = __shfl_xor(bv, 32, 64);
+        const int oi = __shfl_xor(bi, 32, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        if (kg == 0) { av[wave * 32 * G + 32 * g + row] = bv; ai[wave * 32 * G + 32 * g + row] = bi; }
+    }
+    amax_combine<4>(p, av, ai, 32 * G, tid, stride, col);
 }
 
 // AW (round 5, "all refills unconditional"): hipcc's vmcnt bookkeeping gives up on the ring loop as written below -- every refill sits behind `if (chunk
@@ -815,71 +873,9 @@ __global__ __launch_bounds__(256) void k_gemv32(GemvArgs p, int ntiles32) {
     }
     float bestv = -INFINITY;
     int besti = 0x7fffffff;
-    if (active && kp == 0 && xok) {
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int nl = 8 * g4 + 4 * kg;                      // first of this quad's 4 consecutive weight rows
-            if constexpr (MODE == GV_SWIGLU) {
-                if (g4 < 2) {
-                    float o[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float g = rbf(acc[g4 * 4 + r]), u = rbf(acc[(g4 + 2) * 4 + r]);
-                        o[r] = rbf(silu_f(g)) * u;
-                    }
-                    bf16_t* ob = reinterpret_cast<bf16_t*>(p.out);
-                    *reinterpret_cast<uint2*>(ob + (p.out_tiled ? tiled_offset((size_t)m, (size_t)(tile * 16 + nl), (size_t)(p.N / 2))
-                                                                : (size_t)m * (p.N / 2) + tile * 16 + nl)) = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
-                }
-            } else if constexpr (MODE == GV_BIAS || MODE == GV_RESID) {
-                const int n = tile * 32 + nl;
-                bf16_t* optr = reinterpret_cast<bf16_t*>(p.out) + (size_t)m * p.ldo + n;
-                float o[4] = {acc[g4 * 4], acc[g4 * 4 + 1], acc[g4 * 4 + 2], acc[g4 * 4 + 3]};
-                if (MODE == GV_BIAS && p.bias) {
-                    const uint2 b = *reinterpret_cast<const uint2*>(p.bias + n);
-                    o[0] += lo16(b.x); o[1] += hi16(b.x); o[2] += lo16(b.y); o[3] += hi16(b.y);
-                }
-                if constexpr (MODE == GV_RESID) {
-                    const uint2 rv = *reinterpret_cast<const uint2*>(optr);
-                    o[0] = lo16(rv.x) + rbf(o[0]); o[1] = hi16(rv.x) + rbf(o[1]);
-                    o[2] = lo16(rv.y) + rbf(o[2]); o[3] = hi16(rv.y) + rbf(o[3]);
-                }
-                const uint2 ov = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
-                *reinterpret_cast<uint2*>(optr) = ov;
-            } else {
-                const int n = tile * 32 + nl;
-                const size_t oi = ((size_t)(MODE == GV_PARTIAL ? blockIdx.y : 0) * p.M + m) * p.N + n;
-                const float4 ov = float4{acc[g4 * 4], acc[g4 * 4 + 1], acc[g4 * 4 + 2], acc[g4 * 4 + 3]};
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + oi) = ov;
-                if constexpr (MODE == GV_F32) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (acc[g4 * 4 + r] > bestv || (acc[g4 * 4 + r] == bestv && n + r < besti)) { bestv = acc[g4 * 4 + r]; besti = n + r; }
-                }
-            }
-        }
-    }
+    if (active && kp == 0 && xok) store32<MODE, false>(p, tile, m, kg, blockIdx.y, acc, &bestv, &besti);
     if constexpr (MODE == GV_F32) {
-        if (p.amax_val) {                                          // KP == 1: smem is free
-            float* av = reinterpret_cast<float*>(smem);            // [WAVES][32]
-            int* ai = reinterpret_cast<int*>(av + WAVES * 32);
-            const float ov = __shfl_xor(bestv, 32, 64);
-            const int oi = __shfl_xor(besti, 32, 64);
-            if (ov > bestv || (ov == bestv && oi < besti)) { bestv = ov; besti = oi; }
-            if (kg == 0) { av[wave * 32 + m] = bestv; ai[wave * 32 + m] = besti; }
-            __syncthreads();
-            if (tid < p.M) {
-                float bv = av[tid];
-                int bi = ai[tid];
-                for (int w2 = 1; w2 < WAVES; ++w2) {
-                    const float v2 = av[w2 * 32 + tid];
-                    const int i2 = ai[w2 * 32 + tid];
-                    if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; }
-                }
-                p.amax_val[(size_t)tid * gridDim.x + blockIdx.x] = bv;
-                p.amax_idx[(size_t)tid * gridDim.x + blockIdx.x] = bi;
-            }
-        }
+        if (p.amax_val) amax32<1>(p, reinterpret_cast<float*>(smem), &bestv, &besti, m, kg, wave, tid, gridDim.x, blockIdx.x);      // KP == 1: smem is free
     }
     TGV(3);
 }
@@ -972,18 +968,7 @@ __global__ __launch_bounds__(256) void k_gemv32_px(GemvArgs p, int ntiles32) {
         if (kp == 0) {
 #pragma unroll
             for (int k = 1; k < KP; ++k) rb_add(rb, k - 1, lane, acc);
-            if (xok) {
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    float4 o = float4{acc[g4 * 4], acc[g4 * 4 + 1], acc[g4 * 4 + 2], acc[g4 * 4 + 3]};
-                    if constexpr (F8) {        // per-output-channel scale of the fp8 weights
-                        const float4 sc = *reinterpret_cast<const float4*>(p.w_scale + (size_t)tile * 32 + 8 * g4 + 4 * kg);
-                        o.x *= sc.x; o.y *= sc.y; o.z *= sc.z; o.w *= sc.w;
-                    }
-                    const size_t oi = ((size_t)slab * p.M + m) * p.N + tile * 32 + 8 * g4 + 4 * kg;
-                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + oi) = o;
-                }
-            }
+            if (xok) store32<GV_PARTIAL, F8>(p, tile, m, kg, slab, acc);
         }
         if (next >= ntiles32) break;
         tile = next;
@@ -1003,8 +988,7 @@ __global__ __launch_bounds__(256) void k_gemv32_hpx(GemvArgs p, int ntiles32, in
     constexpr int NCH = 32;                     // K = 2048 (launcher)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     bf16_t* xs = reinterpret_cast<bf16_t*>(smem);                               // [2 row groups][32 chunks][2 halves][64 lanes][8]: x as it lies in memory
-    float* av = reinterpret_cast<float*>(smem + (size_t)32 * 2048 * 2);        // [4 waves][32 rows]
-    int* ai = reinterpret_cast<int*>(av + 4 * 32);
+    float* av = reinterpret_cast<float*>(smem + (size_t)32 * 2048 * 2);        // [4 waves][32 rows] values, then as many indices (amax32)
     TGV(0);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, half = (lane >> 4) & 1, kg = lane >> 5, m = lane & 31;
@@ -1065,34 +1049,10 @@ __global__ __launch_bounds__(256) void k_gemv32_hpx(GemvArgs p, int ntiles32, in
         else run_tile(std::false_type{}, tile, 0, acc);
         float bestv = -INFINITY;
         int besti = 0x7fffffff;
-        if (active && xok) {
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int n = tile * 32 + 8 * g4 + 4 * kg;
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)m * p.N + n) = float4{acc[g4 * 4], acc[g4 * 4 + 1], acc[g4 * 4 + 2], acc[g4 * 4 + 3]};
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (acc[g4 * 4 + r] > bestv || (acc[g4 * 4 + r] == bestv && n + r < besti)) { bestv = acc[g4 * 4 + r]; besti = n + r; }
-            }
-        }
+        if (active && xok) store32<GV_F32, false>(p, tile, m, kg, 0, acc, &bestv, &besti);
         if (p.amax_val) {        // the group's arg-max partial, as one block of the streaming launch computes it
-            const float ov = __shfl_xor(bestv, 32, 64);
-            const int oi = __shfl_xor(besti, 32, 64);
-            if (ov > bestv || (ov == bestv && oi < besti)) { bestv = ov; besti = oi; }
-            if (kg == 0) { av[wave * 32 + m] = bestv; ai[wave * 32 + m] = besti; }
-            __syncthreads();
-            if (tid < p.M) {
-                float bv = av[tid];
-                int bi = ai[tid];
-                for (int w2 = 1; w2 < 4; ++w2) {
-                    const float v2 = av[w2 * 32 + tid];
-                    const int i2 = ai[w2 * 32 + tid];
-                    if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; }
-                }
-                p.amax_val[(size_t)tid * ngroups + g] = bv;
-                p.amax_idx[(size_t)tid * ngroups + g] = bi;
-            }
-            __syncthreads();
+            amax32<1>(p, av, &bestv, &besti, m, kg, wave, tid, ngroups, g);
+            __syncthreads();     // (the next group's partials must not meet a slow reader)
         }
         if (!more) break;
         g = gnext;
@@ -1215,18 +1175,6 @@ __global__ __launch_bounds__(256, G <= 2 ? 2 : 1) void k_gemv32g(GemvArgs p, int
                 for (int g = 0; g < G; ++g) rb_add(smem, (tp * (KP - 1) + (k - 1)) * G + g, lane, acc[g]);
         }
     }
-    if constexpr (F8) {
-        if (active && kp == 0) {        // per-output-channel scale of the fp8 weights (engine row order): weight row of acc[i] = tile * 32 + 8 (i / 4) + 4 kg + i % 4
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const float4 sc = *reinterpret_cast<const float4*>(p.w_scale + (size_t)tile * 32 + 8 * g4 + 4 * kg);
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    acc[g][g4 * 4] *= sc.x; acc[g][g4 * 4 + 1] *= sc.y; acc[g][g4 * 4 + 2] *= sc.z; acc[g][g4 * 4 + 3] *= sc.w;
-                }
-            }
-        }
-    }
     float bestv[G];
     int besti[G];
 #pragma unroll
@@ -1234,75 +1182,32 @@ __global__ __launch_bounds__(256, G <= 2 ? 2 : 1) void k_gemv32g(GemvArgs p, int
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int m = m0 + 32 * g;
-        if (!(active && kp == 0 && m < p.M)) continue;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int nl = 8 * g4 + 4 * kg;
-            if constexpr (MODE == GV_SWIGLU) {
-                if (g4 < 2) {
-                    float o[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float gt = rbf(acc[g][g4 * 4 + r]), up = rbf(acc[g][(g4 + 2) * 4 + r]);
-                        o[r] = rbf(silu_f(gt)) * up;
-                    }
-                    bf16_t* ob = reinterpret_cast<bf16_t*>(p.out);
-                    *reinterpret_cast<uint2*>(ob + (p.out_tiled ? tiled_offset((size_t)m, (size_t)(tile * 16 + nl), (size_t)(p.N / 2))
-                                                                : (size_t)m * (p.N / 2) + tile * 16 + nl)) = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
-                }
-            } else if constexpr (MODE == GV_BIAS || MODE == GV_RESID) {
-                const int n = tile * 32 + nl;
-                bf16_t* optr = reinterpret_cast<bf16_t*>(p.out) + (size_t)m * p.ldo + n;
-                float o[4] = {acc[g][g4 * 4], acc[g][g4 * 4 + 1], acc[g][g4 * 4 + 2], acc[g][g4 * 4 + 3]};
-                if (MODE == GV_BIAS && p.bias) {
-                    const uint2 b = *reinterpret_cast<const uint2*>(p.bias + n);
-                    o[0] += lo16(b.x); o[1] += hi16(b.x); o[2] += lo16(b.y); o[3] += hi16(b.y);
-                }
-                if constexpr (MODE == GV_RESID) {
-                    const uint2 rv = *reinterpret_cast<const uint2*>(optr);
-                    o[0] = lo16(rv.x) + rbf(o[0]); o[1] = hi16(rv.x) + rbf(o[1]);
-                    o[2] = lo16(rv.y) + rbf(o[2]); o[3] = hi16(rv.y) + rbf(o[3]);
-                }
-                *reinterpret_cast<uint2*>(optr) = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
-            } else {
-                const int n = tile * 32 + nl;
-                float* o = reinterpret_cast<float*>(p.out) + ((size_t)(MODE == GV_PARTIAL ? blockIdx.y : 0) * p.M + m) * p.N + n;
-                *reinterpret_cast<float4*>(o) = float4{acc[g][g4 * 4], acc[g][g4 * 4 + 1], acc[g][g4 * 4 + 2], acc[g][g4 * 4 + 3]};
-                if constexpr (MODE == GV_F32) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (acc[g][g4 * 4 + r] > bestv[g] || (acc[g][g4 * 4 + r] == bestv[g] && n + r < besti[g])) { bestv[g] = acc[g][g4 * 4 + r]; besti[g] = n + r; }
-                }
-            }
-        }
+        if (active && kp == 0 && m < p.M) store32<MODE, F8>(p, tile, m, kg, blockIdx.y, acc[g], &bestv[g], &besti[g]);
     }
     if constexpr (MODE == GV_F32) {
-        if (p.amax_val) {                                          // KP == 1: smem is free
-            float* av = reinterpret_cast<float*>(smem);            // [WAVES][32 G]
-            int* ai = reinterpret_cast<int*>(av + WAVES * 32 * G);
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                float bv = bestv[g];
-                int bi = besti[g];
-                const float ov = __shfl_xor(bv, 32, 64);
-                const int oi = __shfl_xor(bi, 32, 64);
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-                if (kg == 0) { av[wave * 32 * G + 32 * g + m0] = bv; ai[wave * 32 * G + 32 * g + m0] = bi; }
-            }
-            __syncthreads();
-            if (tid < p.M) {
-                float bv = av[tid];
-                int bi = ai[tid];
-                for (int w2 = 1; w2 < WAVES; ++w2) {
-                    const float v2 = av[w2 * 32 * G + tid];
-                    const int i2 = ai[w2 * 32 * G + tid];
-                    if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; }
-                }
-                p.amax_val[(size_t)tid * gridDim.x + blockIdx.x] = bv;
-                p.amax_idx[(size_t)tid * gridDim.x + blockIdx.x] = bi;
-            }
-        }
+        if (p.amax_val) amax32<G>(p, reinterpret_cast<float*>(smem), bestv, besti, m0, kg, wave, tid, gridDim.x, blockIdx.x);      // KP == 1: smem is free
     }
+}
+
+// run-time (mode, kp) -> f(MODE, KP) with both as compile-time constants: THE list of what gets instantiated.  F32 (one wave per tile: the head's summation
+// order) always runs with KP = 1; the fp8 stream knows the in-block K split 4 only, and no F32
+template <int V> using int_c = std::integral_constant<int, V>;
+template <bool F8, class F>
+int with_mode_kp(int mode, int kp, F f) {
+    auto with_kp = [&](auto m) {
+        if constexpr (F8) return kp == 4 ? f(m, int_c<4>{}) : -22;
+        else return kp == 4 ? f(m, int_c<4>{}) : kp == 2 ? f(m, int_c<2>{}) : f(m, int_c<1>{});
+    };
+    switch (mode) {
+        case GV_PARTIAL: return with_kp(int_c<GV_PARTIAL>{});
+        case GV_SWIGLU: return with_kp(int_c<GV_SWIGLU>{});
+        case GV_BIAS: return with_kp(int_c<GV_BIAS>{});
+        case GV_RESID: return with_kp(int_c<GV_RESID>{});
+        case GV_F32:
+            if constexpr (F8) return -22;
+            else return f(int_c<GV_F32>{}, int_c<1>{});
+    }
+    return -22;
 }
 
 template <int MODE, int KP, int G, bool F8 = false>
@@ -1316,22 +1221,13 @@ int launch_32g(hipStream_t s, const GemvArgs& a) {
     SR_CHECK_LAUNCH();
     return 0;
 }
-template <int MODE, int G, bool F8 = false>
-int launch_32g_kp(hipStream_t s, const GemvArgs& a, int kp) {
-    if constexpr (MODE == GV_F32) return launch_32g<MODE, 1, G, false>(s, a);
-    else if constexpr (F8) return kp == 4 ? launch_32g<MODE, 4, G, true>(s, a) : -22;        // (the fp8 stream: in-block K split 4 only, as at <= 32 rows)
-    else return kp == 4 ? launch_32g<MODE, 4, G>(s, a) : kp == 2 ? launch_32g<MODE, 2, G>(s, a) : launch_32g<MODE, 1, G>(s, a);
-}
-template <int G, bool F8 = false>
-int launch_32g_mode(hipStream_t s, const GemvArgs& a, int mode, int kp) {
-    switch (mode) {
-        case GV_PARTIAL: return launch_32g_kp<GV_PARTIAL, G, F8>(s, a, kp);
-        case GV_SWIGLU: return launch_32g_kp<GV_SWIGLU, G, F8>(s, a, kp);
-        case GV_F32: return F8 ? -22 : launch_32g_kp<GV_F32, G, false>(s, a, kp);
-        case GV_BIAS: return launch_32g_kp<GV_BIAS, G, F8>(s, a, kp);
-        case GV_RESID: return launch_32g_kp<GV_RESID, G, F8>(s, a, kp);
-    }
-    return -22;
+// the launch table: g row groups (1 / 2 / 4) per weight pass
+template <bool F8>
+int launch_32g_any(hipStream_t s, const GemvArgs& a, int mode, int kp, int g) {
+    return with_mode_kp<F8>(mode, kp, [&](auto m, auto k) {
+        constexpr int MODE = decltype(m)::value, KP = decltype(k)::value;
+        return g == 1 ? launch_32g<MODE, KP, 1, F8>(s, a) : g == 2 ? launch_32g<MODE, KP, 2, F8>(s, a) : launch_32g<MODE, KP, 4, F8>(s, a);
+    });
 }
 
 // Measured and dropped (round 2): sharing x through LDS at batches 5..32 -- the 4 waves of a block own 4 DIFFERENT weight tiles
@@ -1497,20 +1393,15 @@ bool use_32(const GemvArgs& a, int mode) {
     return mode == GV_F32 || (mode == GV_PARTIAL && a.ksplit >= 4);
 }
 
-int gemv_f32_blocks(int N, int M, int K, int has_norm) {
-    GemvArgs a{};
-    a.M = M; a.K = K; a.N = N;
-    a.norm_w = has_norm ? reinterpret_cast<const bf16_t*>(&a) : nullptr;     // only its null-ness matters here
-    return use_32(a, GV_F32) ? cdiv(N / 32, 4) : cdiv(N / 16, 4);
-}
-
 // vocabulary rows covered by one block of the F32 (LM head) launch = rows per entry of the argmax partials
 int gemv_f32_block_rows(int N, int M, int K, int has_norm) {
     GemvArgs a{};
     a.M = M; a.K = K; a.N = N;
-    a.norm_w = has_norm ? reinterpret_cast<const bf16_t*>(&a) : nullptr;
+    a.norm_w = has_norm ? reinterpret_cast<const bf16_t*>(&a) : nullptr;     // only its null-ness matters here
     return use_32(a, GV_F32) ? 128 : 64;
 }
+
+int gemv_f32_blocks(int N, int M, int K, int has_norm) { return cdiv(N / (gemv_f32_block_rows(N, M, K, has_norm) / 4), 4); }
 
 // largest in-block K split that leaves >= 2 chunks per wave
 int gemv_pick_kp(int K, int ksplit, int want) {
@@ -1525,32 +1416,25 @@ int launch_gemv(hipStream_t s, const GemvArgs& a_, int mode) {
     a.counted = sr_switches().gemv_counted;      // (SR_GEMV_COUNTED=0: the conditional-refill loops of rounds 1-4, A/B and bit-identity hook)
     if (a.M <= 0) return 0;
     if (a.M > 128 || a.K % 64 != 0 || a.N % 16 != 0) return -22;
-    if (a.M > 32) {      // 33..128 rows: the 32-row-tile kernel over 2 / 4 row groups per weight pass (bf16 stream, no fused norm)
+    if (mode == GV_PARTIAL && (a.ksplit < 1 || a.ksplit > a.K / 64)) return -22;
+    if (a.out_tiled && (mode != GV_SWIGLU || (a.N / 2) % 64 != 0)) return -22;
+    const int kp = gemv_pick_kp(a.K, mode == GV_PARTIAL ? a.ksplit : 1, mode == GV_F32 ? 1 : 4);
+    if (a.M > 32) {      // 33..128 rows: the 32-row-tile kernel over 2 / 4 row groups per weight pass (no fused norm)
         if (a.N % 32 != 0 || a.norm_w || a.n_slabs) return -22;
         if (a.W8 && (!a.w_scale || mode == GV_F32)) return -22;
-        if (mode == GV_PARTIAL && (a.ksplit < 1 || a.ksplit > a.K / 64)) return -22;
-        if (a.out_tiled && (mode != GV_SWIGLU || (a.N / 2) % 64 != 0)) return -22;
-        const int kp32 = gemv_pick_kp(a.K, mode == GV_PARTIAL ? a.ksplit : 1, mode == GV_F32 ? 1 : 4);
         // NARROW matrices (q/k/v, o_proj: N = 2560 / 2048 = 80 / 64 tiles): one 32-row group per block and the groups over gridDim.y -- 2 - 4 x the
         // blocks, and their 8 - 10 MB of weights cost nothing to stream once per group (measured against two groups per block: decode step
         // 3.24 -> 3.09 ms at 64 rows, 4.20 -> 4.15 ms at 128; bit-identical)
         const bool narrow = (mode == GV_BIAS || mode == GV_RESID) && a.N <= 4096;
-        if (a.W8) {     // fp8 weight stream (round 5): the same row-group kernel on the tiled8 image
-            if (narrow) return launch_32g_mode<1, true>(s, a, mode, kp32);
-            return a.M <= 64 ? launch_32g_mode<2, true>(s, a, mode, kp32) : launch_32g_mode<4, true>(s, a, mode, kp32);
-        }
-        if (narrow) return launch_32g_mode<1>(s, a, mode, kp32);
-        return a.M <= 64 ? launch_32g_mode<2>(s, a, mode, kp32) : launch_32g_mode<4>(s, a, mode, kp32);
+        const int g = narrow ? 1 : a.M <= 64 ? 2 : 4;
+        // (fp8 weight stream, round 5: the same row-group kernel on the tiled8 image)
+        return a.W8 ? launch_32g_any<true>(s, a, mode, kp, g) : launch_32g_any<false>(s, a, mode, kp, g);
     }
     if (mode == GV_SWIGLU && a.N % 32 != 0) return -22;
-    if (mode == GV_PARTIAL && (a.ksplit < 1 || a.ksplit > a.K / 64)) return -22;
     if (a.norm_w && !(mode == GV_BIAS || mode == GV_SWIGLU || mode == GV_F32)) return -22;
     if (a.norm_w && !can_stage(a)) return -22;
     if (a.n_slabs > 0 && (!a.norm_w || !a.slabs || !a.x_out)) return -22;
     if (a.x_tiled && a.norm_w) return -22;                   // fragment-ordered x: the un-staged paths only
-    if (a.out_tiled && (mode != GV_SWIGLU || (a.N / 2) % 64 != 0)) return -22;
-    int want = mode == GV_F32 ? 1 : 4;
-    const int kp = gemv_pick_kp(a.K, mode == GV_PARTIAL ? a.ksplit : 1, want);
     if (kp == 4 && px_ok(a, mode)) return a.W8 ? launch_px<true>(s, a) : launch_px<false>(s, a);
     if (kp == 4 && px32_ok(a, mode)) return a.W8 ? launch_px32<true>(s, a) : launch_px32<false>(s, a);
     if (hpx_ok(a, mode)) return launch_hpx(s, a);
@@ -1559,30 +1443,9 @@ int launch_gemv(hipStream_t s, const GemvArgs& a_, int mode) {
         if (kp != 4) return -22;
         // 17..32 rows, 4-slab down-projection: the 32-row-tile kernel (x read once per 32 weight rows), as for the bf16 stream -- measured on the fp8
         // stream at 32 rows: decode step 2.211 -> 2.180 ms; gate/up unchanged (2.216), q/k/v + o_proj slower (2.323) and therefore left on 16-row tiles
-        if (mode == GV_PARTIAL && a.M > 16 && a.ksplit >= 4 && a.N % 32 == 0 && !a.norm_w) return launch_32g_mode<1, true>(s, a, mode, kp);
-        switch (mode) {
-            case GV_PARTIAL: return launch_small<GV_PARTIAL, 4, true>(s, a);
-            case GV_SWIGLU: return launch_small<GV_SWIGLU, 4, true>(s, a);
-            case GV_BIAS: return launch_small<GV_BIAS, 4, true>(s, a);
-            case GV_RESID: return launch_small<GV_RESID, 4, true>(s, a);
-        }
-        return -22;
+        if (mode == GV_PARTIAL && a.M > 16 && a.ksplit >= 4 && a.N % 32 == 0 && !a.norm_w) return launch_32g_any<true>(s, a, mode, kp, 1);
+        return with_mode_kp<true>(mode, kp, [&](auto m, auto k) { return launch_small<decltype(m)::value, decltype(k)::value, true>(s, a); });
     }
-    if (use_32(a, mode)) {
-        switch (mode) {
-            case GV_PARTIAL: return kp == 4 ? launch_32<GV_PARTIAL, 4>(s, a) : kp == 2 ? launch_32<GV_PARTIAL, 2>(s, a) : launch_32<GV_PARTIAL, 1>(s, a);
-            case GV_SWIGLU: return kp == 4 ? launch_32<GV_SWIGLU, 4>(s, a) : kp == 2 ? launch_32<GV_SWIGLU, 2>(s, a) : launch_32<GV_SWIGLU, 1>(s, a);
-            case GV_F32: return launch_32<GV_F32, 1>(s, a);
-            case GV_BIAS: return kp == 4 ? launch_32<GV_BIAS, 4>(s, a) : kp == 2 ? launch_32<GV_BIAS, 2>(s, a) : launch_32<GV_BIAS, 1>(s, a);
-            case GV_RESID: return kp == 4 ? launch_32<GV_RESID, 4>(s, a) : kp == 2 ? launch_32<GV_RESID, 2>(s, a) : launch_32<GV_RESID, 1>(s, a);
-        }
-    }
-    switch (mode) {
-        case GV_PARTIAL: return kp == 4 ? launch_small<GV_PARTIAL, 4>(s, a) : kp == 2 ? launch_small<GV_PARTIAL, 2>(s, a) : launch_small<GV_PARTIAL, 1>(s, a);
-        case GV_SWIGLU: return kp == 4 ? launch_small<GV_SWIGLU, 4>(s, a) : kp == 2 ? launch_small<GV_SWIGLU, 2>(s, a) : launch_small<GV_SWIGLU, 1>(s, a);
-        case GV_F32: return launch_small<GV_F32, 1>(s, a);
-        case GV_BIAS: return kp == 4 ? launch_small<GV_BIAS, 4>(s, a) : kp == 2 ? launch_small<GV_BIAS, 2>(s, a) : launch_small<GV_BIAS, 1>(s, a);
-        case GV_RESID: return kp == 4 ? launch_small<GV_RESID, 4>(s, a) : kp == 2 ? launch_small<GV_RESID, 2>(s, a) : launch_small<GV_RESID, 1>(s, a);
-    }
-    return -22;
+    if (use_32(a, mode)) return with_mode_kp<false>(mode, kp, [&](auto m, auto k) { return launch_32<decltype(m)::value, decltype(k)::value>(s, a); });
+    return with_mode_kp<false>(mode, kp, [&](auto m, auto k) { return launch_small<decltype(m)::value, decltype(k)::value>(s, a); });
 }

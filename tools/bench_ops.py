@@ -121,11 +121,12 @@ def bench_gemv(Ms):
         ksd = int(os.environ.get("SR_BENCH_KSD", "4" if M > 16 else "2"))
         s = stream()
         # batches > 4: activations travel in fragment order (engine.hip x_tiled); the values are random either way.  x / act are
-        # over-allocated to 32 rows so that the tiled addressing of a 16-row group stays in bounds
+        # over-allocated to whole 16-row groups (at least 32 rows) so that the tiled addressing of a 16-row group stays in bounds
         XT = 0x800 if (M > 4 and os.environ.get("SR_XTILED", "1") != "0") else 0
         OT = 0x1000 if XT else 0
-        x = torch.empty(32, I, dtype=torch.bfloat16, device=dev).normal_(0, 1)
-        act = torch.empty(32, I, dtype=torch.bfloat16, device=dev).normal_(0, 1)
+        rows = max(32, (M + 15) // 16 * 16)
+        x = torch.empty(rows, I, dtype=torch.bfloat16, device=dev).normal_(0, 1)
+        act = torch.empty(rows, I, dtype=torch.bfloat16, device=dev).normal_(0, 1)
         nbv = lib.sr_op_gemv_f32_blocks(V, M, H, 1 if fused else 0)
         av = torch.empty(M, nbv, dtype=torch.float32, device=dev)
         ai = torch.empty(M, nbv, dtype=torch.int32, device=dev)
