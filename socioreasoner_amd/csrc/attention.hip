@@ -56,6 +56,144 @@ struct PrefillCfg {
     static constexpr int V_BYTES = HD * VT_RS;
 };
 
+// ---------------------------------------------------------------------------------------------- the steps every prefill kernel shares
+// A wave holds 16 queries against 64-key tiles: lane = (query fr = lane & 15, group fg = lane >> 4).  k_attn_prefill, k_attn_win64,
+// k_attn_fewq and k_attn_prefill2 differ in how K and V^T tiles reach the MFMAs, not in the arithmetic below -- every rounding point
+// and mask rule of the bf16 prefill path is written here, once.
+
+// Q fragments of the lane's query row: d = kk * 32 + fg * 8 .. + 7, zero past HD
+template <int HD>
+__device__ __forceinline__ void load_q(const bf16_t* qptr, int fg, bf16x8 (&qf)[PrefillCfg<HD>::KS]) {
+#pragma unroll
+    for (int kk = 0; kk < PrefillCfg<HD>::KS; ++kk) {
+        const int d = kk * 32 + fg * 8;
+        if (d < HD) qf[kk] = *reinterpret_cast<const bf16x8*>(qptr + d);
+        else qf[kk] = __builtin_bit_cast(bf16x8, uint4{0, 0, 0, 0});
+    }
+}
+
+// K rows kv0 .. kv0 + 63 (clamped to the sequence) -> the padded-pitch LDS tile, by threads t, t + nthr, ... (a block or one wave)
+template <int HD>
+__device__ __forceinline__ void stage_k(unsigned char* ks, const bf16_t* kbase, int k_stride, int kv0, int seq_len, int t, int nthr) {
+    using C = PrefillCfg<HD>;
+    constexpr int CH = C::HDP / 8;                       // 16-byte chunks per row (incl. zero padding)
+    for (int c = t; c < KT * CH; c += nthr) {
+        const int row = c / CH, ch = c % CH;
+        uint4 v = uint4{0, 0, 0, 0};
+        if (ch * 8 < HD) {
+            const int j = min(kv0 + row, seq_len - 1);
+            v = *reinterpret_cast<const uint4*>(kbase + (size_t)j * k_stride + ch * 8);
+        }
+        *reinterpret_cast<uint4*>(ks + row * C::K_RS + ch * 16) = v;
+    }
+}
+// V^T columns kv0 .. kv0 + 63 of every d row -> the padded-pitch LDS tile
+template <int HD>
+__device__ __forceinline__ void stage_v(unsigned char* vs, const bf16_t* vbase, int vt_stride, int kv0, int seq_len, int t, int nthr) {
+    for (int c = t; c < HD * (KT / 4); c += nthr) {
+        const int d = c / (KT / 4), g4 = c % (KT / 4);
+        const int j0 = kv0 + g4 * 4;
+        uint2 v = uint2{0, 0};
+        if (j0 < seq_len) {
+            v = *reinterpret_cast<const uint2*>(vbase + (size_t)d * vt_stride + j0);
+            // zero the keys past the end of the sequence (they hold other data or garbage)
+            if (j0 + 1 >= seq_len) v.x &= 0x0000ffffu;
+            if (j0 + 2 >= seq_len) v.y = 0;
+            else if (j0 + 3 >= seq_len) v.y &= 0x0000ffffu;
+        }
+        *reinterpret_cast<uint2*>(vs + d * VT_RS + g4 * 8) = v;
+    }
+}
+
+// raw scores of 16 keys against the wave's 16 queries: acc[r] = key (first + fg * 4 + r) . query fr.  kfrag(kk) hands over the K fragment of
+// MFMA k-step kk (key row fr of the 16, d = kk * 32 + fg * 8 ..) from wherever the kernel keeps it; scaled_scores4 follows
+template <int KS, class KF>
+__device__ __forceinline__ f32x4 qk16(KF&& kfrag, const bf16x8 (&qf)[KS]) {
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfrag(kk), qf[kk], acc, 0, 0, 0);
+    return acc;
+}
+// THE mask rule: keys past the sequence and, when causal, keys after the query (kidx0 = key of s[0])
+template <bool CAUSAL>
+__device__ __forceinline__ void mask4(const float (&sv)[4], int kidx0, int seq_len, int qpos, float (&s)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int kidx = kidx0 + r;
+        const bool ok = kidx < seq_len && (!CAUSAL || kidx <= qpos);
+        s[r] = ok ? sv[r] : -INFINITY;
+    }
+}
+// scores of one staged padded-pitch tile: s[t][r] = key kv0 + t*16 + fg*4 + r against query fr of this wave
+template <int HD, bool CAUSAL>
+__device__ __forceinline__ void scores_padded(const unsigned char* ks, const bf16x8 (&qf)[PrefillCfg<HD>::KS], float scale, int kv0, int seq_len,
+                                              int qpos, int fr, int fg, float (&s)[4][4]) {
+    using C = PrefillCfg<HD>;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const f32x4 acc = qk16<C::KS>([&](int kk) { return *reinterpret_cast<const bf16x8*>(ks + (t * 16 + fr) * C::K_RS + (kk * 4 + fg) * 16); }, qf);
+        float sv[4];
+        scaled_scores4(acc, scale, sv);
+        mask4<CAUSAL>(sv, kv0 + t * 16 + fg * 4, seq_len, qpos, s[t]);
+    }
+}
+
+// row max / sum of exp over a 64-key tile: the lane's 16 scores, then the four lane groups that share a query
+__device__ __forceinline__ float tile_max(const float (&s)[4][4]) {
+    float tm = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tm = fmaxf(tm, s[t][r]);
+    tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
+    return fmaxf(tm, __shfl_xor(tm, 32, 64));
+}
+__device__ __forceinline__ float tile_expsum(const float (&s)[4][4], float mn) {
+    float ts = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ts += __expf(s[t][r] - mn);
+    ts += __shfl_xor(ts, 16, 64);
+    return ts + __shfl_xor(ts, 32, 64);
+}
+// pass 1, one tile: online update of the row max m and of l = sum exp(s - m)
+__device__ __forceinline__ void softmax_step(const float (&s)[4][4], float& m, float& l) {
+    const float mn = fmaxf(m, tile_max(s));
+    l = l * __expf(m - mn) + tile_expsum(s, mn);
+    m = mn;
+}
+// pass 2: P = bf16(exp(s - m) / l) of 32 keys (two scaled_scores4 results of qk16 accumulators) as the B operand of P.V
+__device__ __forceinline__ bf16x8 pack_p(const float (&s0)[4], const float (&s1)[4], float m, float inv_l) {
+    uint4 pv;
+    pv.x = pack2(__expf(s0[0] - m) * inv_l, __expf(s0[1] - m) * inv_l);
+    pv.y = pack2(__expf(s0[2] - m) * inv_l, __expf(s0[3] - m) * inv_l);
+    pv.z = pack2(__expf(s1[0] - m) * inv_l, __expf(s1[1] - m) * inv_l);
+    pv.w = pack2(__expf(s1[2] - m) * inv_l, __expf(s1[3] - m) * inv_l);
+    return __builtin_bit_cast(bf16x8, pv);
+}
+// O^T += V^T . P^T for key block kb (32 keys) of the padded-pitch V^T tile
+template <int DT>
+__device__ __forceinline__ void pv_padded(const unsigned char* vs, int kb, int fr, int fg, const bf16x8& pf, f32x4 (&oacc)[DT]) {
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+        const unsigned char* vr = vs + (dt * 16 + fr) * VT_RS + kb * 64 + fg * 8;
+        uint2 v0 = *reinterpret_cast<const uint2*>(vr);        // keys kb*32 + fg*4 .. +3
+        uint2 v1 = *reinterpret_cast<const uint2*>(vr + 32);   // keys kb*32 + 16 + fg*4 .. +3
+        const bf16x8 vf = __builtin_bit_cast(bf16x8, uint4{v0.x, v0.y, v1.x, v1.y});
+        oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[dt], 0, 0, 0);
+    }
+}
+// the lane's four d of every d-tile, rounded to bf16 (optr: the query's row, column h * HD + fg * 4)
+template <int DT>
+__device__ __forceinline__ void store_o(bf16_t* optr, const f32x4 (&oacc)[DT]) {
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+        uint2 v = {pack2(oacc[dt][0], oacc[dt][1]), pack2(oacc[dt][2], oacc[dt][3])};
+        *reinterpret_cast<uint2*>(optr + dt * 16) = v;
+    }
+}
+
 template <int HD, bool CAUSAL>
 __global__ __launch_bounds__(256) void k_attn_prefill(AttnArgs p) {
     using C = PrefillCfg<HD>;
@@ -73,93 +211,22 @@ __global__ __launch_bounds__(256) void k_attn_prefill(AttnArgs p) {
     const int q_len = wk.q_len > 0 ? wk.q_len : wk.seq_len;      // (pooled queries: fewer queries than keys)
     const bool q_valid = qpos < q_len;
     const int q_rows_valid = min(QT, q_len - wk.q_off);
-    const bf16_t* qptr = p.q + (size_t)(wk.q_row0 + min(q_local, q_rows_valid - 1)) * p.q_stride + h * HD;
-
     bf16x8 qf[C::KS];
-#pragma unroll
-    for (int kk = 0; kk < C::KS; ++kk) {
-        const int d = kk * 32 + fg * 8;
-        if (d < HD) qf[kk] = *reinterpret_cast<const bf16x8*>(qptr + d);
-        else qf[kk] = __builtin_bit_cast(bf16x8, uint4{0, 0, 0, 0});
-    }
+    load_q<HD>(p.q + (size_t)(wk.q_row0 + min(q_local, q_rows_valid - 1)) * p.q_stride + h * HD, fg, qf);
 
     const bf16_t* kbase = p.k + (size_t)wk.k_row0 * p.k_stride + (size_t)kvh * p.k_head_stride;
     const bf16_t* vbase = p.vt + wk.vt_off + (size_t)kvh * p.vt_head_stride;
     const int kv_end = CAUSAL ? min(wk.seq_len, wk.q_off + QT) : wk.seq_len;
 
-    auto stage_k = [&](int kv0) {
-        constexpr int CH = C::HDP / 8;                       // 16-byte chunks per row (incl. zero padding)
-        for (int c = tid; c < KT * CH; c += 256) {
-            const int row = c / CH, ch = c % CH;
-            uint4 v = uint4{0, 0, 0, 0};
-            if (ch * 8 < HD) {
-                const int j = min(kv0 + row, wk.seq_len - 1);
-                v = *reinterpret_cast<const uint4*>(kbase + (size_t)j * p.k_stride + ch * 8);
-            }
-            *reinterpret_cast<uint4*>(ks + row * C::K_RS + ch * 16) = v;
-        }
-    };
-    auto stage_v = [&](int kv0) {
-        for (int c = tid; c < HD * (KT / 4); c += 256) {
-            const int d = c / (KT / 4), g4 = c % (KT / 4);
-            const int j0 = kv0 + g4 * 4;
-            uint2 v = uint2{0, 0};
-            if (j0 < wk.seq_len) {
-                v = *reinterpret_cast<const uint2*>(vbase + (size_t)d * p.vt_stride + j0);
-                // zero the keys past the end of the sequence (they hold other data or garbage)
-                if (j0 + 1 >= wk.seq_len) v.x &= 0x0000ffffu;
-                if (j0 + 2 >= wk.seq_len) v.y = 0;
-                else if (j0 + 3 >= wk.seq_len) v.y &= 0x0000ffffu;
-            }
-            *reinterpret_cast<uint2*>(vs + d * VT_RS + g4 * 8) = v;
-        }
-    };
-    // scores of one staged tile: s[t][r] = key kv0 + t*16 + fg*4 + r against query fr of this wave
-    auto scores = [&](int kv0, float (&s)[4][4]) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < C::KS; ++kk) {
-                bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + (t * 16 + fr) * C::K_RS + (kk * 4 + fg) * 16);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], acc, 0, 0, 0);
-            }
-            float sv[4];
-            scaled_scores4(acc, p.scale, sv);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kidx = kv0 + t * 16 + fg * 4 + r;
-                const bool ok = kidx < wk.seq_len && (!CAUSAL || kidx <= qpos);
-                s[t][r] = ok ? sv[r] : -INFINITY;
-            }
-        }
-    };
-
     // ---------------- pass 1: row max m and sum l = sum exp(s - m)
     float m = -INFINITY, l = 0.f;
     for (int kv0 = 0; kv0 < kv_end; kv0 += KT) {
         __syncthreads();
-        stage_k(kv0);
+        stage_k<HD>(ks, kbase, p.k_stride, kv0, wk.seq_len, tid, 256);
         __syncthreads();
         float s[4][4];
-        scores(kv0, s);
-        float tm = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tm = fmaxf(tm, s[t][r]);
-        tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-        const float mn = fmaxf(m, tm);
-        float ts = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ts += __expf(s[t][r] - mn);
-        ts += __shfl_xor(ts, 16, 64);
-        ts += __shfl_xor(ts, 32, 64);
-        l = l * __expf(m - mn) + ts;
-        m = mn;
+        scores_padded<HD, CAUSAL>(ks, qf, p.scale, kv0, wk.seq_len, qpos, fr, fg, s);
+        softmax_step(s, m, l);
     }
     const float inv_l = 1.0f / l;
 
@@ -169,37 +236,15 @@ __global__ __launch_bounds__(256) void k_attn_prefill(AttnArgs p) {
     for (int dt = 0; dt < C::DT; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kv0 = 0; kv0 < kv_end; kv0 += KT) {
         __syncthreads();
-        stage_k(kv0);
-        stage_v(kv0);
+        stage_k<HD>(ks, kbase, p.k_stride, kv0, wk.seq_len, tid, 256);
+        stage_v<HD>(vs, vbase, p.vt_stride, kv0, wk.seq_len, tid, 256);
         __syncthreads();
         float s[4][4];
-        scores(kv0, s);
+        scores_padded<HD, CAUSAL>(ks, qf, p.scale, kv0, wk.seq_len, qpos, fr, fg, s);
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            uint4 pv;
-            pv.x = pack2(__expf(s[2 * kb][0] - m) * inv_l, __expf(s[2 * kb][1] - m) * inv_l);
-            pv.y = pack2(__expf(s[2 * kb][2] - m) * inv_l, __expf(s[2 * kb][3] - m) * inv_l);
-            pv.z = pack2(__expf(s[2 * kb + 1][0] - m) * inv_l, __expf(s[2 * kb + 1][1] - m) * inv_l);
-            pv.w = pack2(__expf(s[2 * kb + 1][2] - m) * inv_l, __expf(s[2 * kb + 1][3] - m) * inv_l);
-            const bf16x8 pf = __builtin_bit_cast(bf16x8, pv);
-#pragma unroll
-            for (int dt = 0; dt < C::DT; ++dt) {
-                const unsigned char* vr = vs + (dt * 16 + fr) * VT_RS + kb * 64 + fg * 8;
-                uint2 v0 = *reinterpret_cast<const uint2*>(vr);        // keys kb*32 + fg*4 .. +3
-                uint2 v1 = *reinterpret_cast<const uint2*>(vr + 32);   // keys kb*32 + 16 + fg*4 .. +3
-                const bf16x8 vf = __builtin_bit_cast(bf16x8, uint4{v0.x, v0.y, v1.x, v1.y});
-                oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[dt], 0, 0, 0);
-            }
-        }
+        for (int kb = 0; kb < 2; ++kb) pv_padded<C::DT>(vs, kb, fr, fg, pack_p(s[2 * kb], s[2 * kb + 1], m, inv_l), oacc);
     }
-    if (q_valid) {
-        bf16_t* optr = p.out + (size_t)(wk.q_row0 + q_local) * p.out_stride + h * HD + fg * 4;
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) {
-            uint2 v = {pack2(oacc[dt][0], oacc[dt][1]), pack2(oacc[dt][2], oacc[dt][3])};
-            *reinterpret_cast<uint2*>(optr + dt * 16) = v;
-        }
-    }
+    if (q_valid) store_o<C::DT>(p.out + (size_t)(wk.q_row0 + q_local) * p.out_stride + h * HD + fg * 4, oacc);
 }
 
 // ---------------------------------------------------------------------------------------------- 64-token windows, no LDS
@@ -219,15 +264,9 @@ __global__ __launch_bounds__(256) void k_attn_win64(AttnArgs p) {
     const int fr = lane & 15, fg = lane >> 4;
     const bf16_t* kbase = p.k + (size_t)wk.k_row0 * p.k_stride + (size_t)kvh * p.k_head_stride;
     const bf16_t* vbase = p.vt + wk.vt_off + (size_t)kvh * p.vt_head_stride;
-    const bf16x8 zero8 = __builtin_bit_cast(bf16x8, uint4{0, 0, 0, 0});
-    bf16x8 kf[4][C::KS];
+    bf16x8 kf[4][C::KS];         // (K rows are Q rows to the MFMA: same fragment, same zero padding)
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int kk = 0; kk < C::KS; ++kk) {
-            const int d = kk * 32 + fg * 8;
-            kf[t][kk] = d < HD ? *reinterpret_cast<const bf16x8*>(kbase + (size_t)(t * 16 + fr) * p.k_stride + d) : zero8;
-        }
+    for (int t = 0; t < 4; ++t) load_q<HD>(kbase + (size_t)(t * 16 + fr) * p.k_stride, fg, kf[t]);
     bf16x8 vf[C::DT][2];
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt)
@@ -239,54 +278,26 @@ __global__ __launch_bounds__(256) void k_attn_win64(AttnArgs p) {
         }
     bf16x8 qf[4][C::KS];
 #pragma unroll
-    for (int qs = 0; qs < 4; ++qs)
-#pragma unroll
-        for (int kk = 0; kk < C::KS; ++kk) {
-            const int d = kk * 32 + fg * 8;
-            qf[qs][kk] = d < HD ? *reinterpret_cast<const bf16x8*>(p.q + (size_t)(wk.q_row0 + qs * 16 + fr) * p.q_stride + h * HD + d) : zero8;
-        }
+    for (int qs = 0; qs < 4; ++qs) load_q<HD>(p.q + (size_t)(wk.q_row0 + qs * 16 + fr) * p.q_stride + h * HD, fg, qf[qs]);
 #pragma unroll
     for (int qs = 0; qs < 4; ++qs) {
-        float s[4][4];
+        float s[4][4];           // a whole window, every key live: no mask
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < C::KS; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t][kk], qf[qs][kk], acc, 0, 0, 0);
-            scaled_scores4(acc, p.scale, s[t]);
-        }
-        float m = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) m = fmaxf(m, s[t][r]);
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        float l = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) l += __expf(s[t][r] - m);
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        const float inv_l = 1.0f / l;
+        for (int t = 0; t < 4; ++t) scaled_scores4(qk16<C::KS>([&](int kk) { return kf[t][kk]; }, qf[qs]), p.scale, s[t]);
+        // the one tile IS the row: softmax_step from (m, l) = (-inf, 0) gives the same m and l = 0 * exp(-inf) + ts = ts, at the price of
+        // an exp, a multiply and an add per query sub-tile that the compiler may not fold -- so its two halves are called directly
+        const float m = tile_max(s);
+        const float inv_l = 1.0f / tile_expsum(s, m);
         f32x4 oacc[C::DT];
 #pragma unroll
         for (int dt = 0; dt < C::DT; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            uint4 pv;
-            pv.x = pack2(__expf(s[2 * kb][0] - m) * inv_l, __expf(s[2 * kb][1] - m) * inv_l);
-            pv.y = pack2(__expf(s[2 * kb][2] - m) * inv_l, __expf(s[2 * kb][3] - m) * inv_l);
-            pv.z = pack2(__expf(s[2 * kb + 1][0] - m) * inv_l, __expf(s[2 * kb + 1][1] - m) * inv_l);
-            pv.w = pack2(__expf(s[2 * kb + 1][2] - m) * inv_l, __expf(s[2 * kb + 1][3] - m) * inv_l);
-            const bf16x8 pf = __builtin_bit_cast(bf16x8, pv);
+            const bf16x8 pf = pack_p(s[2 * kb], s[2 * kb + 1], m, inv_l);
 #pragma unroll
             for (int dt = 0; dt < C::DT; ++dt) oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt][kb], pf, oacc[dt], 0, 0, 0);
         }
-        bf16_t* optr = p.out + (size_t)(wk.q_row0 + qs * 16 + fr) * p.out_stride + h * HD + fg * 4;
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) *reinterpret_cast<uint2*>(optr + dt * 16) = uint2{pack2(oacc[dt][0], oacc[dt][1]), pack2(oacc[dt][2], oacc[dt][3])};
+        store_o<C::DT>(p.out + (size_t)(wk.q_row0 + qs * 16 + fr) * p.out_stride + h * HD + fg * 4, oacc);
     }
 }
 
@@ -313,78 +324,18 @@ __global__ __launch_bounds__(NW * 64) void k_attn_fewq(AttnArgs p) {
     const int q_len = wk.q_len > 0 ? wk.q_len : wk.seq_len;
     const int nq = min(16, q_len - wk.q_off);                   // live queries (<= 16 by contract: AttnArgs.q_tile == 16)
     const bool q_valid = fr < nq;
-    const bf16_t* qptr = p.q + (size_t)(wk.q_row0 + min(fr, nq - 1)) * p.q_stride + h * HD;
     bf16x8 qf[C::KS];
-#pragma unroll
-    for (int kk = 0; kk < C::KS; ++kk) {
-        const int d = kk * 32 + fg * 8;
-        if (d < HD) qf[kk] = *reinterpret_cast<const bf16x8*>(qptr + d);
-        else qf[kk] = __builtin_bit_cast(bf16x8, uint4{0, 0, 0, 0});
-    }
+    load_q<HD>(p.q + (size_t)(wk.q_row0 + min(fr, nq - 1)) * p.q_stride + h * HD, fg, qf);
     const bf16_t* kbase = p.k + (size_t)wk.k_row0 * p.k_stride + (size_t)kvh * p.k_head_stride;
     const bf16_t* vbase = p.vt + wk.vt_off + (size_t)kvh * p.vt_head_stride;
     const int ntile = (wk.seq_len + KT - 1) / KT;
-    auto stage_k = [&](int kv0) {
-        constexpr int CH = C::HDP / 8;
-        for (int c = lane; c < KT * CH; c += 64) {
-            const int row = c / CH, ch = c % CH;
-            uint4 v = uint4{0, 0, 0, 0};
-            if (ch * 8 < HD) v = *reinterpret_cast<const uint4*>(kbase + (size_t)min(kv0 + row, wk.seq_len - 1) * p.k_stride + ch * 8);
-            *reinterpret_cast<uint4*>(ks + row * C::K_RS + ch * 16) = v;
-        }
-    };
-    auto stage_v = [&](int kv0) {
-        for (int c = lane; c < HD * (KT / 4); c += 64) {
-            const int d = c / (KT / 4), g4 = c % (KT / 4);
-            const int j0 = kv0 + g4 * 4;
-            uint2 v = uint2{0, 0};
-            if (j0 < wk.seq_len) {
-                v = *reinterpret_cast<const uint2*>(vbase + (size_t)d * p.vt_stride + j0);
-                if (j0 + 1 >= wk.seq_len) v.x &= 0x0000ffffu;
-                if (j0 + 2 >= wk.seq_len) v.y = 0;
-                else if (j0 + 3 >= wk.seq_len) v.y &= 0x0000ffffu;
-            }
-            *reinterpret_cast<uint2*>(vs + d * VT_RS + g4 * 8) = v;
-        }
-    };
-    auto scores = [&](int kv0, float (&s)[4][4]) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < C::KS; ++kk) {
-                bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + (t * 16 + fr) * C::K_RS + (kk * 4 + fg) * 16);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], acc, 0, 0, 0);
-            }
-            float sv[4];
-            scaled_scores4(acc, p.scale, sv);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s[t][r] = (kv0 + t * 16 + fg * 4 + r < wk.seq_len) ? sv[r] : -INFINITY;
-        }
-    };
-    // ---- pass 1 over this wave's tiles
+    // ---- pass 1 over this wave's tiles (never causal: no query position)
     float m = -INFINITY, l = 0.f;
     for (int ti = wave; ti < ntile; ti += NW) {
-        stage_k(ti * KT);
+        stage_k<HD>(ks, kbase, p.k_stride, ti * KT, wk.seq_len, lane, 64);
         float s[4][4];
-        scores(ti * KT, s);
-        float tm = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tm = fmaxf(tm, s[t][r]);
-        tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-        const float mn = fmaxf(m, tm);
-        float ts = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ts += __expf(s[t][r] - mn);
-        ts += __shfl_xor(ts, 16, 64);
-        ts += __shfl_xor(ts, 32, 64);
-        l = l * __expf(m - mn) + ts;
-        m = mn;
+        scores_padded<HD, false>(ks, qf, p.scale, ti * KT, wk.seq_len, 0, fr, fg, s);
+        softmax_step(s, m, l);
     }
     if (fg == 0) { ml[(wave * 16 + fr) * 2] = m; ml[(wave * 16 + fr) * 2 + 1] = l; }
     __syncthreads();
@@ -403,42 +354,28 @@ __global__ __launch_bounds__(NW * 64) void k_attn_fewq(AttnArgs p) {
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int ti = wave; ti < ntile; ti += NW) {
-        stage_k(ti * KT);
-        stage_v(ti * KT);
+        stage_k<HD>(ks, kbase, p.k_stride, ti * KT, wk.seq_len, lane, 64);
+        stage_v<HD>(vs, vbase, p.vt_stride, ti * KT, wk.seq_len, lane, 64);
         float s[4][4];
-        scores(ti * KT, s);
+        scores_padded<HD, false>(ks, qf, p.scale, ti * KT, wk.seq_len, 0, fr, fg, s);
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            uint4 pv;
-            pv.x = pack2(__expf(s[2 * kb][0] - gm) * inv_l, __expf(s[2 * kb][1] - gm) * inv_l);
-            pv.y = pack2(__expf(s[2 * kb][2] - gm) * inv_l, __expf(s[2 * kb][3] - gm) * inv_l);
-            pv.z = pack2(__expf(s[2 * kb + 1][0] - gm) * inv_l, __expf(s[2 * kb + 1][1] - gm) * inv_l);
-            pv.w = pack2(__expf(s[2 * kb + 1][2] - gm) * inv_l, __expf(s[2 * kb + 1][3] - gm) * inv_l);
-            const bf16x8 pf = __builtin_bit_cast(bf16x8, pv);
-#pragma unroll
-            for (int dt = 0; dt < C::DT; ++dt) {
-                const unsigned char* vr = vs + (dt * 16 + fr) * VT_RS + kb * 64 + fg * 8;
-                const uint2 v0 = *reinterpret_cast<const uint2*>(vr), v1 = *reinterpret_cast<const uint2*>(vr + 32);
-                oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, uint4{v0.x, v0.y, v1.x, v1.y}), pf, oacc[dt], 0, 0, 0);
-            }
-        }
+        for (int kb = 0; kb < 2; ++kb) pv_padded<C::DT>(vs, kb, fr, fg, pack_p(s[2 * kb], s[2 * kb + 1], gm, inv_l), oacc);
     }
     // the wave's partial sums go into its own (now dead) staging region
 #pragma unroll
     for (int dt = 0; dt < C::DT; ++dt) reinterpret_cast<f32x4*>(ks)[dt * 64 + lane] = oacc[dt];
     __syncthreads();
     if (wave == 0 && q_valid) {
-        bf16_t* optr = p.out + (size_t)(wk.q_row0 + fr) * p.out_stride + h * HD + fg * 4;
 #pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) {
-            f32x4 o = reinterpret_cast<const f32x4*>(smem)[dt * 64 + lane];
+        for (int dt = 0; dt < C::DT; ++dt) {                    // P.V partial sums added in wave order
+            oacc[dt] = reinterpret_cast<const f32x4*>(smem)[dt * 64 + lane];
 #pragma unroll
             for (int w = 1; w < NW; ++w) {
                 const f32x4 o2 = reinterpret_cast<const f32x4*>(smem + w * WB)[dt * 64 + lane];
-                o[0] += o2[0]; o[1] += o2[1]; o[2] += o2[2]; o[3] += o2[3];
+                oacc[dt][0] += o2[0]; oacc[dt][1] += o2[1]; oacc[dt][2] += o2[2]; oacc[dt][3] += o2[3];
             }
-            *reinterpret_cast<uint2*>(optr + dt * 16) = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
         }
+        store_o<C::DT>(p.out + (size_t)(wk.q_row0 + fr) * p.out_stride + h * HD + fg * 4, oacc);
     }
 }
 
@@ -542,11 +479,7 @@ __global__ __launch_bounds__(512, 4) void k_attn_prefill2(AttnArgs p, int n_unit
     extern __shared__ __attribute__((aligned(16))) unsigned char smem2[];
 
     // block -> (work item, head group, query sub-tile); XCD x (blocks x, x + 8, ...) takes a contiguous run of units
-    int unit;
-    {
-        const int flat = blockIdx.x, q8 = n_units / 8, r8 = n_units % 8, xcd = flat % 8, idx = flat / 8;
-        unit = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
+    const int unit = xcd_contiguous(blockIdx.x, n_units);
     const AttnWork wk0 = p.work[unit / (Y * subs)];
     const int h0 = ((unit / subs) % Y) * NH, sub = unit % subs;
     const int q_off = wk0.q_off + sub * QTB;
@@ -561,15 +494,8 @@ __global__ __launch_bounds__(512, 4) void k_attn_prefill2(AttnArgs p, int n_unit
     const int qpos = q_off + q_local;
     const bool q_valid = qpos < q_len;
     const int q_rows_valid = min(QTB, q_len - q_off);
-    const bf16_t* qptr = p.q + (size_t)(q_row0 + min(q_local, q_rows_valid - 1)) * p.q_stride + h * HD;
     bf16x8 qf[C::KS];
-#pragma unroll
-    for (int kk = 0; kk < C::KS; ++kk) {
-        const int d = kk * 32 + fg * 8;
-        if (d < HD) qf[kk] = *reinterpret_cast<const bf16x8*>(qptr + d);
-        else qf[kk] = __builtin_bit_cast(bf16x8, uint4{0, 0, 0, 0});
-    }
-
+    load_q<HD>(p.q + (size_t)(q_row0 + min(q_local, q_rows_valid - 1)) * p.q_stride + h * HD, fg, qf);
     // hipcc must see the Q fragments ARRIVE before the tile loop: it does not count the asm DMA below, so a wait for these loads placed
     // inside the loop (`vmcnt(0)` at their first use, repeated on every iteration) would drain the ring each step
 #pragma unroll
@@ -617,21 +543,11 @@ __global__ __launch_bounds__(512, 4) void k_attn_prefill2(AttnArgs p, int n_unit
     // instruction-issue bound (PMC round 3: ~3800 instructions per wave, 4 waves per SIMD, ACTIVE_INST_ANY x 4 = 113 % of the wave cycles),
     // and the two compares + select per score are 15 % of them
     auto scores16 = [&](const unsigned char* ks, int kv0, int t, float (&s)[4], bool masked) {
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < C::KS; ++kk) {
-            bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + (t * 16 + fr) * 256 + (((kk * 4 + fg) ^ fr) << 4));
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], acc, 0, 0, 0);
-        }
+        const f32x4 acc = qk16<C::KS>([&](int kk) { return *reinterpret_cast<const bf16x8*>(ks + (t * 16 + fr) * 256 + (((kk * 4 + fg) ^ fr) << 4)); }, qf);
         if (masked) {
             float sv[4];
             scaled_scores4(acc, p.scale, sv);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kidx = kv0 + t * 16 + fg * 4 + r;
-                const bool ok = kidx < seq_len && (!CAUSAL || kidx <= qpos);
-                s[r] = ok ? sv[r] : -INFINITY;
-            }
+            mask4<CAUSAL>(sv, kv0 + t * 16 + fg * 4, seq_len, qpos, s);
         } else {
             scaled_scores4(acc, p.scale, s);
         }
@@ -673,23 +589,7 @@ __global__ __launch_bounds__(512, 4) void k_attn_prefill2(AttnArgs p, int n_unit
             float s[4][4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) scores16(ks, kv0, t, s[t], masked);
-            float tm = -INFINITY;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) tm = fmaxf(tm, s[t][r]);
-            tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-            tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-            const float mn = fmaxf(m, tm);
-            float ts = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ts += __expf(s[t][r] - mn);
-            ts += __shfl_xor(ts, 16, 64);
-            ts += __shfl_xor(ts, 32, 64);
-            l = l * __expf(m - mn) + ts;
-            m = mn;
+            softmax_step(s, m, l);
             if (u == nt - 1) inv_l = 1.0f / l;
         } else {
             // ---------------- pass 2: P = bf16(exp(s - m) / l);  O^T += V^T . P^T   (32 keys at a time: fewer live registers)
@@ -700,12 +600,7 @@ __global__ __launch_bounds__(512, 4) void k_attn_prefill2(AttnArgs p, int n_unit
                 float s0[4], s1[4];
                 scores16(ks, kv0, 2 * kb, s0, masked);
                 scores16(ks, kv0, 2 * kb + 1, s1, masked);
-                uint4 pv;
-                pv.x = pack2(__expf(s0[0] - m) * inv_l, __expf(s0[1] - m) * inv_l);
-                pv.y = pack2(__expf(s0[2] - m) * inv_l, __expf(s0[3] - m) * inv_l);
-                pv.z = pack2(__expf(s1[0] - m) * inv_l, __expf(s1[1] - m) * inv_l);
-                pv.w = pack2(__expf(s1[2] - m) * inv_l, __expf(s1[3] - m) * inv_l);
-                const bf16x8 pf = __builtin_bit_cast(bf16x8, pv);
+                const bf16x8 pf = pack_p(s0, s1, m, inv_l);
                 if constexpr (VASM) {
                     const unsigned a0 = lds0 + buf * ST_BYTES + vo[kb][0], a1 = lds0 + buf * ST_BYTES + vo[kb][1];
                     u32x2 v0[C::DT], v1[C::DT];
@@ -735,14 +630,7 @@ __global__ __launch_bounds__(512, 4) void k_attn_prefill2(AttnArgs p, int n_unit
         __builtin_amdgcn_sched_barrier(0);
         buf = buf + 1 == NS ? 0 : buf + 1;
     }
-    if (q_valid) {
-        bf16_t* optr = p.out + (size_t)(q_row0 + q_local) * p.out_stride + h * HD + fg * 4;
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) {
-            uint2 v = {pack2(oacc[dt][0], oacc[dt][1]), pack2(oacc[dt][2], oacc[dt][3])};
-            *reinterpret_cast<uint2*>(optr + dt * 16) = v;
-        }
-    }
+    if (q_valid) store_o<C::DT>(p.out + (size_t)(q_row0 + q_local) * p.out_stride + h * HD + fg * 4, oacc);
 }
 
 // ---------------------------------------------------------------------------------------------- decode (q_len = 1)
@@ -1053,72 +941,99 @@ extern "C" __attribute__((visibility("default"))) int sr_dbg_attn_dec_times(long
 }
 #endif
 
+// raises a kernel's dynamic-LDS limit on its first launch
+template <auto KERNEL>
+static int dyn_lds_once(int bytes) {
+    static bool done = false;
+    if (!done) {
+        hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (r != hipSuccess) return (int)r;
+        done = true;
+    }
+    return 0;
+}
+
 template <int HD, bool CAUSAL, int QW, int NS, bool VASM>
 static int launch_prefill2(hipStream_t s, const AttnArgs& a) {
     constexpr int NH = 8 / QW, QTB = QW * 16;
     constexpr int smem = NS * (KT * 256 + HD * 128);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_prefill2<HD, CAUSAL, QW, NS, VASM>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (r != hipSuccess) return (int)r;
-        attr = true;
-    }
+    if (int rc = dyn_lds_once<k_attn_prefill2<HD, CAUSAL, QW, NS, VASM>>(smem)) return rc;
     const int Y = a.n_heads / NH, subs = a.q_tile / QTB, n_units = a.n_work * Y * subs;
     hipLaunchKernelGGL((k_attn_prefill2<HD, CAUSAL, QW, NS, VASM>), dim3(n_units), dim3(512), smem, s, a, n_units, Y, subs);
     SR_CHECK_LAUNCH();
     return 0;
 }
+template <int HD, bool CAUSAL>
+static int launch_prefill1(hipStream_t s, const AttnArgs& a) {
+    hipLaunchKernelGGL((k_attn_prefill<HD, CAUSAL>), dim3(a.n_work, a.n_heads), dim3(256), 0, s, a);
+    SR_CHECK_LAUNCH();
+    return 0;
+}
 
-// which kernel takes the launch: 2 = k_attn_prefill2 (8-wave blocks sharing LDS-DMA-staged tiles; needs a.v2_ok from the caller:
-// 16-byte aligned V^T key runs with finite contents, work items cut at a.q_tile queries), 1 = k_attn_prefill.  SR_ATTN2=0 forces the
-// round-2 kernel (the bit-identity tests flip it and call sr_switches_reload).
+// THE table of the bf16 prefill attention: which kernel takes a launch, or that none does (-22).  The checks run in this order (the
+// preconditions at sr_op_attention in include/socior.h are its documented form):
+//   k_attn_prefill2 (8-wave blocks sharing LDS-DMA-staged tiles) needs a.v2_ok from the caller -- 16-byte aligned V^T key runs with finite
+//     contents, work items cut at a.q_tile queries; SR_ATTN2=0 turns it off (the bit-identity tests flip it and call sr_switches_reload);
+//   k_attn_win64 needs a.win64: every item = one 64-token window starting at its first query (caller's promise); SR_ATTN_WIN64=0 turns
+//     it off, and the launch falls through to the rows below;
+//   k_attn_fewq takes work items of <= 16 queries (SAM2 token-to-image attention): the waves of a block split the keys;
+//   k_attn_prefill walks 64-query work items.
+enum AttnPath { ATTN_REFUSE, ATTN_PREFILL2_LM, ATTN_PREFILL2_VIT, ATTN_WIN64, ATTN_FEWQ,
+                ATTN_PREFILL_80, ATTN_PREFILL_128_CAUSAL, ATTN_PREFILL_128, ATTN_PREFILL_16, ATTN_PREFILL_32 };
+static AttnPath attn_prefill_path(const AttnArgs& a, int head_dim, const SrSwitches& sw) {
+    if (sw.attn2 && a.v2_ok) {
+        if (head_dim == 128 && a.causal && a.q_tile == 64 && a.group % 4 == 0 && a.n_heads % 4 == 0) return ATTN_PREFILL2_LM;
+        if (head_dim == 80 && !a.causal && a.q_tile == 128 && a.group == 1) return ATTN_PREFILL2_VIT;
+    }
+    if (a.win64 && head_dim == 80 && !a.causal && a.n_heads % 4 == 0 && sw.attn_win64) return ATTN_WIN64;
+    if (a.q_tile == 16) return a.causal || head_dim != 16 ? ATTN_REFUSE : ATTN_FEWQ;
+    if (a.q_tile != 0 && a.q_tile != 64) return ATTN_REFUSE;
+    if (a.causal) return head_dim == 128 ? ATTN_PREFILL_128_CAUSAL : ATTN_REFUSE;
+    switch (head_dim) {
+        case 80: return ATTN_PREFILL_80;
+        case 128: return ATTN_PREFILL_128;
+        case 16: return ATTN_PREFILL_16;      // SAM2 mask decoder: cross attention
+        case 32: return ATTN_PREFILL_32;      //                    token self-attention
+        default: return ATTN_REFUSE;
+    }
+}
+
+// 2 = k_attn_prefill2 takes the launch, 1 = one of the others (the engine asks before it hands over work items cut at 128 queries)
 int attn_prefill_variant(const AttnArgs& a, int head_dim) {
-    if (!sr_switches().attn2) return 1;
-    if (!a.v2_ok) return 1;
-    if (head_dim == 128 && a.causal && a.q_tile == 64 && a.group % 4 == 0 && a.n_heads % 4 == 0) return 2;
-    if (head_dim == 80 && !a.causal && a.q_tile == 128 && a.group == 1) return 2;
-    return 1;
+    const AttnPath path = attn_prefill_path(a, head_dim, sr_switches());
+    return path == ATTN_PREFILL2_LM || path == ATTN_PREFILL2_VIT ? 2 : 1;
 }
 
 int launch_attn_prefill(hipStream_t s, const AttnArgs& a, int head_dim) {
     if (a.n_work <= 0) return 0;
-    if (attn_prefill_variant(a, head_dim) == 2) {
-        const bool vasm = sr_switches().attn_vasm;          // hand-issued ds_read_b64 for V^T (bit-identical; SR_ATTN_VASM=0: the compiler's ds_read2st64_b64)
-        if (head_dim == 128) return vasm ? launch_prefill2<128, true, 2, 2, true>(s, a) : launch_prefill2<128, true, 2, 2, false>(s, a);       // 32 queries x 4 heads, 2 x 32 KB ring
-        return vasm ? launch_prefill2<80, false, 8, 3, true>(s, a) : launch_prefill2<80, false, 8, 3, false>(s, a);                            // 128 queries x 1 head, 3 x 26 KB ring
-    }
-    if (a.win64 && head_dim == 80 && !a.causal && a.n_heads % 4 == 0) {      // every item = one 64-token window starting at its first query (caller's promise)
-        if (sr_switches().attn_win64) {
+    const SrSwitches& sw = sr_switches();
+    const bool vasm = sw.attn_vasm;          // hand-issued ds_read_b64 for V^T (bit-identical; SR_ATTN_VASM=0: the compiler's ds_read2st64_b64)
+    switch (attn_prefill_path(a, head_dim, sw)) {
+        case ATTN_PREFILL2_LM:       // 32 queries x 4 heads, 2 x 32 KB ring
+            return vasm ? launch_prefill2<128, true, 2, 2, true>(s, a) : launch_prefill2<128, true, 2, 2, false>(s, a);
+        case ATTN_PREFILL2_VIT:      // 128 queries x 1 head, 3 x 26 KB ring
+            return vasm ? launch_prefill2<80, false, 8, 3, true>(s, a) : launch_prefill2<80, false, 8, 3, false>(s, a);
+        case ATTN_WIN64:
             hipLaunchKernelGGL((k_attn_win64<80>), dim3(a.n_work, a.n_heads / 4), dim3(256), 0, s, a);
             SR_CHECK_LAUNCH();
             return 0;
+        case ATTN_FEWQ: {
+            // 16 waves per block: 4 key tiles per wave and pass at 4096 keys (8 waves: 8 tiles; mask decoder for one object 0.64 -> 0.60 ms)
+            constexpr int NW = 16;
+            constexpr int smem = NW * (PrefillCfg<16>::K_BYTES + PrefillCfg<16>::V_BYTES) + NW * 16 * 8;
+            if (int rc = dyn_lds_once<k_attn_fewq<16, NW>>(smem)) return rc;
+            hipLaunchKernelGGL((k_attn_fewq<16, NW>), dim3(a.n_work, a.n_heads), dim3(NW * 64), smem, s, a);
+            SR_CHECK_LAUNCH();
+            return 0;
         }
+        case ATTN_PREFILL_80: return launch_prefill1<80, false>(s, a);
+        case ATTN_PREFILL_128_CAUSAL: return launch_prefill1<128, true>(s, a);
+        case ATTN_PREFILL_128: return launch_prefill1<128, false>(s, a);
+        case ATTN_PREFILL_16: return launch_prefill1<16, false>(s, a);
+        case ATTN_PREFILL_32: return launch_prefill1<32, false>(s, a);
+        case ATTN_REFUSE: break;
     }
-    if (a.q_tile == 16) {      // work items of <= 16 queries (SAM2 token-to-image attention): the waves of a block split the keys
-        if (a.causal || head_dim != 16) return -22;
-        // 16 waves per block: 4 key tiles per wave and pass at 4096 keys (8 waves: 8 tiles; mask decoder for one object 0.64 -> 0.60 ms)
-        constexpr int NW = 16;
-        constexpr int smem = NW * (PrefillCfg<16>::K_BYTES + PrefillCfg<16>::V_BYTES) + NW * 16 * 8;
-        static bool attr = false;
-        if (!attr) {
-            hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_fewq<16, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (r != hipSuccess) return (int)r;
-            attr = true;
-        }
-        hipLaunchKernelGGL((k_attn_fewq<16, NW>), dim3(a.n_work, a.n_heads), dim3(NW * 64), smem, s, a);
-        SR_CHECK_LAUNCH();
-        return 0;
-    }
-    if (a.q_tile != 0 && a.q_tile != 64) return -22;           // k_attn_prefill walks 64-query work items
-    dim3 grid(a.n_work, a.n_heads), block(256);
-    if (head_dim == 80 && !a.causal) hipLaunchKernelGGL((k_attn_prefill<80, false>), grid, block, 0, s, a);
-    else if (head_dim == 128 && a.causal) hipLaunchKernelGGL((k_attn_prefill<128, true>), grid, block, 0, s, a);
-    else if (head_dim == 128 && !a.causal) hipLaunchKernelGGL((k_attn_prefill<128, false>), grid, block, 0, s, a);
-    else if (head_dim == 16 && !a.causal) hipLaunchKernelGGL((k_attn_prefill<16, false>), grid, block, 0, s, a);      // SAM2 mask decoder: cross attention
-    else if (head_dim == 32 && !a.causal) hipLaunchKernelGGL((k_attn_prefill<32, false>), grid, block, 0, s, a);      //                    token self-attention
-    else return -22;
-    SR_CHECK_LAUNCH();
-    return 0;
+    return -22;
 }
 
 static size_t dec_smem(int ctx_max, int group, int dtiles = 2) { return (size_t)dtiles * 3 * 64 * 16 + (size_t)group * (ctx_max + 8) * sizeof(bf16_t); }

@@ -37,6 +37,13 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Block bid of an nblk-block 1-D grid runs on XCD bid % 8.  Returns the work unit it should take so that every XCD works on ONE
+// contiguous run of units (neighbouring units share operands: they then share that XCD's L2); bijective for any grid size.
+__device__ __forceinline__ int xcd_contiguous(int bid, int nblk) {
+    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, idx = bid / 8;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 // HF: F.silu on a bf16 tensor = float32 x * sigmoid(x), one rounding (hf:85-96 act_fn)
 __device__ __forceinline__ float silu_f(float x) { return x * (1.0f / (1.0f + __expf(-x))); }
 // nn.GELU() (erf form), float32 internally

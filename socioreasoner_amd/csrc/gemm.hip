@@ -47,11 +47,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmArgs p, int ntm, int ntn) 
 
     // ---- block -> tile: XCD-aware (block b runs on XCD b % 8: give each XCD a contiguous run of tiles), then
     // grouped ordering (8 m-tiles share their W panels while walking n)
-    int bid = blockIdx.x, nblk = gridDim.x;
-    {
-        int q = nblk / 8, r = nblk % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
     constexpr int GROUP = 8;
     int per_group = GROUP * ntn;
     int gid = bid / per_group;

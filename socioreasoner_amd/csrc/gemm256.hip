@@ -62,12 +62,7 @@ __global__ __launch_bounds__(512) void k_gemm256(GemmArgs p, int ntm, int ntn, i
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // ONE array (a second __shared__ object de-pipelines)
     T256(0, wall_clock64());
     T256(4, ((long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4));
-    int bid = blockIdx.x;
-    const int nblk = gridDim.x;
-    {   // XCD-aware: block b runs on XCD b % 8 -> give every XCD a contiguous run of tiles (bijective for any grid size)
-        const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);      // XCD-aware: every XCD takes a contiguous run of tiles
     // GROUP m-tiles share their W panels while walking n
     const int per_group = GROUP * ntn;
     const int gid = bid / per_group, first_m = gid * GROUP, gsz = min(ntm - first_m, GROUP);

@@ -203,11 +203,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32s(GemmF32Args p, int n_tiles
     // tile order (as gemm256.hip): block b runs on XCD b % 8 -> every XCD gets a contiguous run of tiles, and inside it FGROUP m-tiles walk the n-tiles
     // together, so that the blocks in flight on an XCD share their W panels (and their A panels) in ITS L2.  With the plain m-major order the
     // XCDs each streamed all of W once per m-tile from the memory side (1.4 GB for the 8192 x 4608 x 1152 launch against 59 MB of operands)
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x, q = nblk / 8, r = nblk % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int ntm = gridDim.x / n_tiles_n, per_group = FGROUP * n_tiles_n;
     const int gid = bid / per_group, first_m = gid * FGROUP, gsz = min(ntm - first_m, FGROUP);
     const int m0 = (first_m + (bid % per_group) % gsz) * GB, n0 = ((bid % per_group) / gsz) * GB;
