@@ -53,8 +53,9 @@ typedef struct sr_config {
     int32_t max_new_tokens;      /* rows of the device token log */
     /* storage of the LM decoder linears (q/k/v, o, gate/up, down) -- BASELINE.json configs[4]:
      *   0 = bf16;  1 = fp8 e4m3 with one float32 scale per output channel, W[n,k] = q[n,k] * scale[n], scale[n] = amax_n / 448.
-     * Embedding / LM head and the ViT stay bf16.  The decode GEMV streams the fp8 image (half the HBM bytes) and widens it to
-     * bf16 in registers (exact); prefill multiplies a bf16 image of the same q; both apply scale[n] to the float32 accumulator.
+     * Embedding / LM head stay bf16; the ViT has a switch of its own (v_weight_dtype below).  The decode GEMV streams the fp8 image
+     * (half the HBM bytes) and widens it to bf16 in registers (exact); prefill multiplies a bf16 image of the same q; both apply
+     * scale[n] to the float32 accumulator.
      *   2 = 1, and the PREFILL linears run fp8 x fp8 on the block-scaled K = 128 MFMA (twice the bf16 rate): their inputs are
      * quantised to OCP-MX e4m3 (32-wide blocks along k, e8m0 shared scales; definition: oracle/model_ref.py mx_quantize), the
      * weight operand is the same fp8 image; decode is unchanged (bf16 activations). */
@@ -62,6 +63,17 @@ typedef struct sr_config {
     /* KV-cache slots, 0 = max_batch.  More slots than batch rows let an admission (sr_admit_stage) prefill the NEXT sequences into
      * spare slots while all max_batch rows are still decoding; sr_admit_commit then maps freed rows onto those slots. */
     int32_t kv_slots;
+    /* storage of the vision tower's linears -- visual.blocks.N.{attn.qkv, attn.proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj}.weight and
+     * visual.merger.mlp.{0,2}.weight; independent of lm_weight_dtype (all six combinations are valid):
+     *   0 = bf16 (the default);
+     *   2 = the definition of lm_weight_dtype = 2 applied to the tower: weights fp8 e4m3 with one float32 scale per output channel
+     * (scale[n] = amax_n / 448), the INPUT of each of these linears quantised to OCP-MX e4m3 after its bf16 rounding (32-wide blocks along
+     * k, e8m0 shared scales; oracle/model_ref.py mx_quantize), fp8 x fp8 on the block-scaled K = 128 MFMA at any row count, the accumulator
+     * multiplied by scale[n], then bias / residual / activation with the bf16 rounding points of mode 0.  The patch embedding (K = 1176,
+     * padded to 1216: no multiple of 128; 0.4 % of the tower's FLOPs), norm weights, biases, rotary tables and attention stay bf16.  The
+     * bf16 masters are kept: sr_finalize_weights quantises from them, and again after any reload.
+     *   1 is refused: fp8 weights under bf16 activations pay for a decode weight stream, which the tower does not have. */
+    int32_t v_weight_dtype;
 } sr_config;
 
 /* Bytes of device workspace sr_engine_create needs for this configuration (0 on invalid config). */
@@ -365,6 +377,18 @@ int sr_op_pixel_shuffle_add_f32(const float* g, int ldg, const float* feat, int 
 int sr_op_quant_mx(const void* x, int ldx, int M, int K, void* q, void* scales, int rows_pad, void* stream);
 int sr_op_gemm_mx(const void* A8, int lda, const void* a_scale, int a_rows_pad, const void* W8, const float* w_scale, int M, int N, int K, void* out,
                   int ldo, const void* bias, const void* resid, int epilogue, void* stream);
+/* The vision tower's fp8 mode (sr_config.v_weight_dtype = 2) at op level:
+ *   sr_op_rmsnorm_mx    : per-row RMSNorm over C channels fused with the MX quantiser -- the bytes of sr_op_rmsnorm (its wave-per-row form)
+ *                         followed by sr_op_quant_mx on the [rows / group][group * C] view (`group` normalised rows = one GEMM row)
+ *   sr_op_gemm_mx_vit   : sr_op_gemm_mx with the operands the tower's epilogues need beyond it: a destination row map (epilogues 0 / 1 / 3),
+ *                         and for epilogue 6 (qkv Linear + 2-D rotary on the PAIRED q / k channel order + V^T write; N = 3 * heads * head_dim)
+ *                         the float32 tables [row][head_dim / 2] and V^T [N / 3][vt_stride]; epilogue 3 = GELU
+ *   sr_op_quant_f8_rows : fp8 image (tiled8) + per-channel scales of a ROW-MAJOR bf16 matrix [N][K], which is left unchanged */
+int sr_op_rmsnorm_mx(const void* x, const void* w, void* q, void* scales, int rows, int C, int group, int rows_pad, float eps, void* stream);
+int sr_op_gemm_mx_vit(const void* A8, int lda, const void* a_scale, int a_rows_pad, const void* W8, const float* w_scale, int M, int N, int K, void* out,
+                      int ldo, const void* bias, const void* resid, const int32_t* rowmap, const float* cos_t, const float* sin_t, void* vt, int vt_stride,
+                      int head_dim, int epilogue, void* stream);
+int sr_op_quant_f8_rows(const void* w, int N, int K, void* w8, float* scale, void* stream);
 int sr_op_gemv(const void* x, int ldx, const void* W, int M, int N, int K, void* out, int ksplit, int mode, void* stream);
 /* decode GEMV with its fusions (mode 3 = bias epilogue, 4 = residual epilogue in place; norm_w != NULL = RMSNorm
  * prologue, optionally after adding n_slabs float32 slabs [n_slabs][M][K]; amax_* = per-block argmax partials of the

@@ -51,6 +51,17 @@ def _get(obj, name, default=None):
     return getattr(obj, name, default)
 
 
+def _vision_quantization(sc: dict):
+    """strategy_config.vision_quantization -> Engine(vit_fp8=...): unset / none / bf16 = the bf16 vision tower, fp8_mx = its linears fp8 x fp8
+    on the block-scaled MFMA.  Anything else is an error by name (a typo must not silently serve bf16)."""
+    v = str(sc.get("vision_quantization", "") or "").lower()
+    if v in ("", "none", "bf16"):
+        return False
+    if v == "fp8_mx":
+        return "mx"
+    raise ValueError(f"strategy_config.vision_quantization {v!r}: 'fp8_mx' or unset (fp8 weights under bf16 activations have no use in the vision tower)")
+
+
 class Mi355xStrategy(InferenceStrategy):
     strategy_name = "mi355x"
     request_stream = True      # start_server may stay open while prompts keep arriving (GenerateScheduler.open_stream; the two-stage pipeline's streamed mode)
@@ -99,6 +110,7 @@ class Mi355xStrategy(InferenceStrategy):
                              max_prefill_tokens=int(sc.get("max_prefill_tokens", min(prompt_len, 2048) * self.max_batch)),
                              max_batch=self.max_batch, max_ctx=max_ctx, max_new_tokens=min(resp_len, max_ctx - 1),
                              lm_fp8={"fp8": True, "fp8_e4m3": True, "fp8_mx": "mx"}.get(str(sc.get("quantization", "") or "").lower(), False),   # vLLM's knob name; fp8_mx: + MX fp8 activations in prefill
+                             vit_fp8=_vision_quantization(sc),       # vision_quantization: fp8_mx -- the tower's own switch, not implied by `quantization`
                              device=f"cuda:{int(_get(getattr(self.worker, 'rank_info', None), 'local_rank', 0) or 0)}")
         if kind == "dir":
             self.engine.load_safetensors_dir(path)

@@ -136,10 +136,11 @@ def geometry_from_hf_config(cfg: dict) -> ModelGeometry:
                          eos_token_id=int(eos[0] if isinstance(eos, (list, tuple)) else eos), pad_token_id=int(cfg.get("pad_token_id", tc.get("pad_token_id", d.pad_token_id)) or d.pad_token_id))
 
 
-def check_supported(g: ModelGeometry, tie_word_embeddings=True) -> None:
+def check_supported(g: ModelGeometry, tie_word_embeddings=True, vit_fp8=False) -> None:
     """Refuses, by name, every checkpoint geometry the engine's kernels cannot run CORRECTLY (a ``config.json`` of another
     Qwen2.5-VL size used to be accepted here and fail -- or, for an untied LM head, silently compute with the embedding matrix -- later).
-    The limits are those of libsocior.so as built for SocioReasoner-3B (csrc/engine.hip ``validate``; include/socior.h)."""
+    The limits are those of libsocior.so as built for SocioReasoner-3B (csrc/engine.hip ``validate``; include/socior.h).
+    vit_fp8 ("mx"): additionally the widths the fp8 vision tower (sr_config.v_weight_dtype = 2) needs -- asked for only with the mode."""
     v, t = g.vision, g.text
     why = []
     if tie_word_embeddings is False:
@@ -165,6 +166,17 @@ def check_supported(g: ModelGeometry, tie_word_embeddings=True) -> None:
         why.append(f"vision out_hidden_size {v.out_hidden_size} != text hidden_size {t.hidden_size}")
     if len(v.fullatt_block_indexes) > 16:
         why.append("more than 16 full-attention blocks")
+    if vit_fp8 not in (False, None, "mx"):
+        why.append(f"vit_fp8 {vit_fp8!r}: False or 'mx'")
+    elif vit_fp8:
+        # the block-scaled fp8 GEMM takes K in 128-wide k-tiles (two at least) and N in 256-column tiles
+        ip, mh = (v.intermediate_size + 63) // 64 * 64, v.hidden_size * v.spatial_merge_size ** 2
+        for what, val, mult in (("vision hidden_size", v.hidden_size, 256), ("vision intermediate_size padded to 64", ip, 128),
+                                ("vision hidden_size x merge^2", mh, 256), ("vision out_hidden_size", v.out_hidden_size, 256)):
+            if val % mult:
+                why.append(f"vit_fp8: {what} {val} is not a multiple of {mult} (K of the block-scaled fp8 GEMM comes in 128-wide k-tiles, N in 256-column tiles)")
+        if ip < 256:
+            why.append(f"vit_fp8: vision intermediate_size padded to 64 is {ip}: at least 256 (two k-tiles)")
     if why:
         raise ValueError("this checkpoint geometry is not supported by the MI355X engine (built for SocioReasoner-3B = Qwen2.5-VL-3B):\n  - " + "\n  - ".join(why))
 

@@ -428,6 +428,24 @@ __global__ __launch_bounds__(256) void k_quant_f8(bf16_t* W, int K, unsigned cha
 // MX activation quantiser of the fp8 prefill path (BASELINE.json configs[4]; definition: oracle/model_ref.py mx_quantize, OCP
 // Microscaling v1.0 with e4m3 elements): per row and 32-wide k-block, shared scale X = 2^(floor(log2(max|v|)) - 8) (e8m0, clamped
 // to 2^-127..2^127; an all-zero block takes 2^-127), elements = fp8_e4m3(v / X) with round-to-nearest-even and saturation to +-448.
+// The three steps both quantiser kernels share: the block's exponent from its maximum, 1 / X, and four elements -> one dword of fp8.
+__device__ __forceinline__ int mx_block_exp(float amax) {
+    // floor(log2(amax)) from the exponent field (bf16 inputs widened to float32 are normal or zero)
+    const int e = (amax > 0.f) ? (int)((__float_as_uint(amax) >> 23) & 255) - 127 - 8 : -127;
+    return max(-127, min(127, e));
+}
+__device__ __forceinline__ float mx_inv_scale(int e) {
+    const float inv = __uint_as_float((uint32_t)(127 - e) << 23);          // 2^-e, exact (127 - e in 0..254; e = 127 -> 2^-127 is subnormal:
+    return (e == 127) ? 5.877471754111438e-39f : inv;                      //  written out, the shift above would give 0)
+}
+__device__ __forceinline__ int mx_cvt4(float v0, float v1, float v2, float v3, float inv2) {
+    const float a0 = fminf(fmaxf(v0 * inv2, -448.f), 448.f), a1 = fminf(fmaxf(v1 * inv2, -448.f), 448.f);
+    const float a2 = fminf(fmaxf(v2 * inv2, -448.f), 448.f), a3 = fminf(fmaxf(v3 * inv2, -448.f), 448.f);
+    int w = 0;
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, w, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(a2, a3, w, true);
+    return w;
+}
 // One thread per block: 64 B in, 32 B out; the 4 scale bytes of a row's 128-wide k-tile are contiguous: scales[k/128][row][4].
 __global__ __launch_bounds__(256) void k_quant_mx_act(const bf16_t* x, int ldx, int M, int K, unsigned char* q, unsigned char* scales, int rows_pad) {
     const int nb = K / 32;
@@ -445,25 +463,108 @@ __global__ __launch_bounds__(256) void k_quant_mx_act(const bf16_t* x, int ldx, 
     float amax = 0.f;
 #pragma unroll
     for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    // floor(log2(amax)) from the exponent field (bf16 inputs widened to float32 are normal or zero)
-    int e = (amax > 0.f) ? (int)((__float_as_uint(amax) >> 23) & 255) - 127 - 8 : -127;
-    e = max(-127, min(127, e));
-    const float inv = __uint_as_float((uint32_t)(127 - e) << 23);          // 2^-e, exact (127 - e in 0..254; e = 127 -> 2^-127 is subnormal:
-    const float inv2 = (e == 127) ? 5.877471754111438e-39f : inv;          //  written out, the shift above would give 0)
+    const int e = mx_block_exp(amax);
+    const float inv2 = mx_inv_scale(e);
     int p[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        float a0 = fminf(fmaxf(v[4 * i + 0] * inv2, -448.f), 448.f), a1 = fminf(fmaxf(v[4 * i + 1] * inv2, -448.f), 448.f);
-        float a2 = fminf(fmaxf(v[4 * i + 2] * inv2, -448.f), 448.f), a3 = fminf(fmaxf(v[4 * i + 3] * inv2, -448.f), 448.f);
-        int w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(a2, a3, w, true);
-        p[i] = w;
-    }
+    for (int i = 0; i < 8; ++i) p[i] = mx_cvt4(v[4 * i + 0], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], inv2);
     uint4* dst = reinterpret_cast<uint4*>(q + (size_t)m * K + b * 32);
     dst[0] = uint4{(uint32_t)p[0], (uint32_t)p[1], (uint32_t)p[2], (uint32_t)p[3]};
     dst[1] = uint4{(uint32_t)p[4], (uint32_t)p[5], (uint32_t)p[6], (uint32_t)p[7]};
     scales[((size_t)(b >> 2) * rows_pad + m) * 4 + (b & 3)] = (unsigned char)(e + 127);
+}
+
+// The vision tower's RMSNorm (k_rmsnorm, one wave per row: same loads, same order of the float32 sums, same two roundings) with the MX
+// quantiser fused: the normalised bf16 row stays in registers and leaves as fp8 bytes + e8m0 block scales -- the bytes launch_rmsnorm
+// (per_wave) followed by k_quant_mx_act write, without the bf16 round trip through HBM (v_weight_dtype 2: nothing else reads v_xn).
+// A lane's 8 channels are a quarter of a 32-wide block: lanes 4j .. 4j + 3 of one pass share the block, its maximum is two lane exchanges.
+// group: `group` consecutive normalised rows of C channels form ONE row of the GEMM operand ([rows / group][group * C]: the merger's
+// ln_q normalises rows of 1280, mlp.0 multiplies [N / 4][5120]); the element bytes are the same linear memory, the scale block is
+// laid out for the merged view.
+template <int MAXC>
+__global__ __launch_bounds__(256) void k_rmsnorm_mx(const bf16_t* xin, const bf16_t* w, unsigned char* q, unsigned char* scales, int rows, int H,
+                                                    float eps, int group, int rows_pad) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int nch = H / 8;
+    float v[MAXC][8];
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+        const int c = lane + i * 64;
+        if (c < nch) {
+            uint4 u = *reinterpret_cast<const uint4*>(xin + (size_t)row * H + c * 8);
+            v[i][0] = lo16(u.x); v[i][1] = hi16(u.x); v[i][2] = lo16(u.y); v[i][3] = hi16(u.y);
+            v[i][4] = lo16(u.z); v[i][5] = hi16(u.z); v[i][6] = lo16(u.w); v[i][7] = hi16(u.w);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ss += v[i][e] * v[i][e];
+        }
+    }
+    ss = wave_sum(ss);
+    const float rs = 1.0f / sqrtf(ss / (float)H + eps);
+    const int m = row / group, b0 = (row % group) * (H / 32);              // GEMM row, first 32-wide block of this normalised row inside it
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+        const int c = lane + i * 64;                                       // (H % 32 == 0: the four lanes of a block are in or out together)
+        float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (c < nch) {
+            uint4 wu = *reinterpret_cast<const uint4*>(w + c * 8);
+            float wv[8] = {lo16(wu.x), hi16(wu.x), lo16(wu.y), hi16(wu.y), lo16(wu.z), hi16(wu.z), lo16(wu.w), hi16(wu.w)};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = rbf(wv[e] * rbf(v[i][e] * rs));      // the bf16 value k_rmsnorm stores
+        }
+        float amax = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(o[e]));
+        amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+        if (c < nch) {
+            const int e = mx_block_exp(amax);
+            const float inv2 = mx_inv_scale(e);
+            const int p0 = mx_cvt4(o[0], o[1], o[2], o[3], inv2), p1 = mx_cvt4(o[4], o[5], o[6], o[7], inv2);
+            *reinterpret_cast<uint2*>(q + (size_t)row * H + c * 8) = uint2{(uint32_t)p0, (uint32_t)p1};
+            const int b = b0 + (c >> 2);
+            if ((lane & 3) == 0) scales[((size_t)(b >> 2) * rows_pad + m) * 4 + (b & 3)] = (unsigned char)(e + 127);
+        }
+    }
+}
+
+// fp8 image of a ROW-MAJOR bf16 matrix [N][ld] (the vision tower keeps its weights row-major): same definition as k_quant_f8 (scale[n] =
+// amax_n / 448, 1 for a zero row; q = fp8(W / scale)), written as the tiled8 image the block-scaled GEMM stages.  The bf16 master is
+// left as it is, so a reload can quantise the matrix again.  One block per 16-row tile, 16 threads per row.
+__global__ __launch_bounds__(256) void k_quant_f8_rows(const bf16_t* W, int K, unsigned char* W8, float* scale) {
+    __shared__ float amax_s[16][17];
+    __shared__ float sc_s[16];
+    const int tid = threadIdx.x, r = tid >> 4, t16 = tid & 15, n = blockIdx.x * 16 + r;
+    const bf16_t* wr = W + (size_t)n * K;
+    float mx = 0.f;
+    for (int k = t16 * 8; k < K; k += 128) {
+        const uint4 u = *reinterpret_cast<const uint4*>(wr + k);
+        const float f[8] = {lo16(u.x), hi16(u.x), lo16(u.y), hi16(u.y), lo16(u.z), hi16(u.z), lo16(u.w), hi16(u.w)};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(f[e]));
+    }
+    amax_s[r][t16] = mx;
+    __syncthreads();
+    if (tid < 16) {
+        float m = 0.f;
+        for (int j = 0; j < 16; ++j) m = fmaxf(m, amax_s[tid][j]);
+        const float sc = m > 0.f ? __fdiv_rn(m, 448.0f) : 1.0f;
+        sc_s[tid] = sc;
+        scale[blockIdx.x * 16 + tid] = sc;
+    }
+    __syncthreads();
+    const float sc = sc_s[r];
+    for (int k = t16 * 8; k < K; k += 128) {
+        const uint4 u = *reinterpret_cast<const uint4*>(wr + k);
+        const float f[8] = {lo16(u.x), hi16(u.x), lo16(u.y), hi16(u.y), lo16(u.z), hi16(u.z), lo16(u.w), hi16(u.w)};
+        int p0 = 0, p1 = 0;
+        p0 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[0], sc), __fdiv_rn(f[1], sc), p0, false);
+        p0 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[2], sc), __fdiv_rn(f[3], sc), p0, true);
+        p1 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[4], sc), __fdiv_rn(f[5], sc), p1, false);
+        p1 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[6], sc), __fdiv_rn(f[7], sc), p1, true);
+        *reinterpret_cast<uint2*>(W8 + tiled8_offset((size_t)n, (size_t)k, (size_t)K)) = uint2{(uint32_t)p0, (uint32_t)p1};
+    }
 }
 }  // namespace
 
@@ -603,6 +704,21 @@ int launch_quant_mx_act(hipStream_t s, const bf16_t* x, int ldx, int M, int K, u
     if (K % 128 != 0 || ldx % 8 != 0 || rows_pad < M) return -22;
     const long long n = (long long)M * (K / 32);
     hipLaunchKernelGGL(k_quant_mx_act, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, M, K, q, scales, rows_pad);
+    SR_CHECK_LAUNCH();
+    return 0;
+}
+int launch_rmsnorm_mx(hipStream_t s, const bf16_t* x, const bf16_t* w, unsigned char* q, unsigned char* scales, int rows, int H, float eps, int group, int rows_pad) {
+    if (rows <= 0) return 0;
+    if (H % 128 != 0 || H > 64 * 8 * 12 || group < 1 || rows % group != 0 || rows_pad < rows / group) return -22;
+    dim3 g(cdiv(rows, 4)), b(256);
+    if (H <= 2048) hipLaunchKernelGGL((k_rmsnorm_mx<4>), g, b, 0, s, x, w, q, scales, rows, H, eps, group, rows_pad);      // (the same split as launch_rmsnorm)
+    else hipLaunchKernelGGL((k_rmsnorm_mx<12>), g, b, 0, s, x, w, q, scales, rows, H, eps, group, rows_pad);
+    SR_CHECK_LAUNCH();
+    return 0;
+}
+int launch_quant_f8_rows(hipStream_t s, const bf16_t* W, int N, int K, unsigned char* W8, float* scale) {
+    if (N % 16 || K % 128) return -22;
+    hipLaunchKernelGGL(k_quant_f8_rows, dim3(N / 16), dim3(256), 0, s, W, K, W8, scale);
     SR_CHECK_LAUNCH();
     return 0;
 }

@@ -30,7 +30,13 @@ thread_local char g_err[512] = "ok";
 constexpr int MAXB = 128;     // batch rows an engine can be configured with (the reference's request-level mode keeps up to 128 requests
                               // in flight per worker: /root/reference/roll/distributed/scheduler/generate_scheduler.py:57)
 constexpr int SPLITK_KS = 4, SPLITK_ROWS = 1024;      // split-K of the residual GEMMs of small prefills (prefill_splitk below)
-struct VitBlockW { bf16_t *norm1, *qkv_w, *qkv_b, *proj_w, *proj_b, *norm2, *gu_w, *gu_b, *down_w, *down_b; };
+struct VitBlockW {
+    bf16_t *norm1, *qkv_w, *qkv_b, *proj_w, *proj_b, *norm2, *gu_w, *gu_b, *down_w, *down_b;
+    // v_weight_dtype = 2: fp8 images (tiled8) + per-output-channel scales of the four linears, quantised FROM the bf16 masters above (which stay)
+    unsigned char *qkv_w8 = nullptr, *proj_w8 = nullptr, *gu_w8 = nullptr, *down_w8 = nullptr;
+    float *qkv_s = nullptr, *proj_s = nullptr, *gu_s = nullptr, *down_s = nullptr;
+    unsigned char dirty[4] = {0, 0, 0, 0};      // a tensor of the matrix was (re)loaded since its last quantisation
+};
 struct LmLayerW {
     bf16_t *ln1, *qkv_w, *qkv_b, *o_w, *ln2, *gu_w, *down_w;
     // lm_weight_dtype = 1: fp8 images (tiled8) + per-output-channel scales of the four linears (null in bf16 mode)
@@ -128,6 +134,7 @@ struct sr_engine {
     bf16_t* patch_w;
     std::vector<VitBlockW> vb;
     bf16_t *ln_q, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+    unsigned char *fc1_w8 = nullptr, *fc2_w8 = nullptr; float *fc1_s = nullptr, *fc2_s = nullptr; unsigned char fc_dirty[2] = {0, 0};   // v_weight_dtype 2 (as VitBlockW)
     bf16_t *embed, *final_norm;
     std::vector<LmLayerW> ll;
     bf16_t* lut;       // [3*256] normalise LUT
@@ -139,6 +146,9 @@ struct sr_engine {
     bool v_paired = false;       // ViT q / k channels stored in the paired order (head_dim / 2 % 8 == 0): see vit_qk_perm
     float *v_cos, *v_sin;
     int *v_rowmap_embed, *v_rowmap_merge;
+    // v_weight_dtype 2: MX-quantised GEMM input of the tower's linears (elements + e8m0 scales [K/128][v_rows_pad][4]); the tower's own, so a
+    // ViT pass on one stream never meets a prefill's t_q8 / t_qs on another
+    unsigned char *v_q8 = nullptr, *v_qs = nullptr; int v_rows_pad = 0; size_t v_qs_bytes = 0;
     AttnWork *v_work_win, *v_work_full, *v_work_full128;     // full attention: 64-query items (k_attn_prefill) and 128-query items (k_attn_prefill2)
     int v_nwork_full128; bool v_full_aligned;
     bool v_win_all64;              // every window of the cached grids is a full 8 x 8 merge-unit window (64 tokens): k_attn_win64 applies
@@ -247,6 +257,26 @@ const char* validate(const sr_config& c) {
         return "lm_weight_dtype 2: the block-scaled fp8 GEMM needs hidden and q/k/v widths in multiples of 256";
     if (c.lm_weight_dtype == 2 && ((c.t_inter + 63) / 64 * 64) % 128)
         return "lm_weight_dtype 2: the MX activation quantiser needs the padded intermediate size (t_inter rounded up to 64) in multiples of 128";
+    if (c.v_weight_dtype != 0 && c.v_weight_dtype != 2)
+        return "v_weight_dtype 0 (bf16) or 2 (fp8 e4m3 weights x MX fp8 activations on the block-scaled MFMA); v_weight_dtype 1 (fp8 weights under bf16 "
+               "activations) exists for a decode weight stream and the vision tower has none";
+    if (c.v_weight_dtype == 2) {
+        // every K the tower's MX GEMMs see must be whole 128-wide k-tiles, every N whole 256-column tiles (q | k | v sections on tile boundaries)
+        static thread_local char why[256];
+        const int ip = (c.v_inter + 63) / 64 * 64, mh = c.v_hidden * c.v_merge * c.v_merge;
+        const struct { const char* what; int v, mult; } need[] = {
+            {"vision hidden_size (K of qkv / gate / up, N of proj / down, q | k | v sections)", c.v_hidden, 256},
+            {"vision intermediate_size padded to 64 (K of down_proj)", ip, 128},
+            {"vision hidden_size x merge^2 (K and N of merger.mlp.0, K of merger.mlp.2)", mh, 256},
+            {"vision out_hidden_size (N of merger.mlp.2)", c.v_out_hidden, 256}};
+        for (const auto& n : need)
+            if (n.v % n.mult) {
+                snprintf(why, sizeof why, "v_weight_dtype 2: %s = %d is not a multiple of %d (the block-scaled fp8 GEMM takes K in 128-wide k-tiles and N in "
+                         "256-column tiles)", n.what, n.v, n.mult);
+                return why;
+            }
+        if (ip < 256) return "v_weight_dtype 2: vision intermediate_size padded to 64 must be at least 256 (two 128-wide k-tiles)";
+    }
     if (c.max_patches < 4 || c.max_patches % 4 || c.max_prefill_tokens < 1 || c.max_new_tokens < 1) return "capacities";
     if (c.v_n_fullatt < 0 || c.v_n_fullatt > 16 || c.v_depth < 1 || c.t_layers < 1) return "depths";
     return nullptr;
@@ -315,6 +345,22 @@ void carve(sr_engine* e) {
     e->inv_freq = ar.take<float>(64);
     e->rope_cos = ar.take<bf16_t>((size_t)(c.max_ctx + 1) * 64);
     e->rope_sin = ar.take<bf16_t>((size_t)(c.max_ctx + 1) * 64);
+    if (c.v_weight_dtype == 2) {
+        for (auto& b : e->vb) {
+            b.qkv_w8 = ar.take<unsigned char>((size_t)3 * C * C);
+            b.proj_w8 = ar.take<unsigned char>((size_t)C * C);
+            b.gu_w8 = ar.take<unsigned char>((size_t)2 * e->v_inter_pad * C);
+            b.down_w8 = ar.take<unsigned char>((size_t)C * e->v_inter_pad);
+            b.qkv_s = ar.take<float>(3 * C);
+            b.proj_s = ar.take<float>(C);
+            b.gu_s = ar.take<float>(2 * e->v_inter_pad);
+            b.down_s = ar.take<float>(C);
+        }
+        e->fc1_w8 = ar.take<unsigned char>((size_t)e->v_mh * e->v_mh);
+        e->fc2_w8 = ar.take<unsigned char>((size_t)c.v_out_hidden * e->v_mh);
+        e->fc1_s = ar.take<float>(e->v_mh);
+        e->fc2_s = ar.take<float>(c.v_out_hidden);
+    }
     e->weights_end = ar.off;
 
     // ViT activations
@@ -335,6 +381,13 @@ void carve(sr_engine* e) {
     e->v_work_win = ar.take<AttnWork>(NP / 4 + 64);
     e->v_work_full = ar.take<AttnWork>(NP / 64 + 64);
     e->v_work_full128 = ar.take<AttnWork>(NP / 128 + 64);
+    if (c.v_weight_dtype == 2) {      // sized by max_patches: [NP][C], [NP][inter_pad] and the merged [NP / 4][4 C] all fit NP * max(C, inter_pad) bytes
+        e->v_rows_pad = (int)((NP + 255) / 256 * 256);
+        const size_t kmax = std::max((size_t)e->v_inter_pad, (size_t)C);
+        e->v_q8 = ar.take<unsigned char>(NP * kmax);
+        e->v_qs_bytes = (std::max(kmax, (size_t)e->v_mh) / 128 + 1) * (size_t)e->v_rows_pad * 4;
+        e->v_qs = ar.take<unsigned char>(e->v_qs_bytes);
+    }
 
     // LM prefill activations
     const size_t TP = c.max_prefill_tokens;
@@ -602,6 +655,21 @@ int lm_gemm(sr_engine* e, hipStream_t s, const bf16_t* A, int lda, const bf16_t*
         a.rope = *rope;
         if (gemm_fuses_lmqkv(a)) { epi = EPI_LMQKV; *fused = true; }
     }
+    SR_TRY(launch_gemm256_mx(s, a, epi));
+    return 0;
+}
+
+// one linear of the vision tower.  v_weight_dtype 0: the bf16 MFMA GEMM on the row-major master, exactly the launch `gemm` makes.  Mode 2: the
+// input is MX-quantised into the tower's own staging buffers (A == nullptr: k_rmsnorm_mx has already left it there) and multiplied with
+// the matrix's fp8 image by the block-scaled MFMA -- as in lm_gemm at ANY row count, so that an image's embedding does not depend on what
+// else is in the call.
+int vit_gemm(sr_engine* e, hipStream_t s, const bf16_t* A, int lda, const bf16_t* W, const unsigned char* W8, const float* w_scale, int M, int N,
+             int K, void* out, int ldo, const bf16_t* bias, const bf16_t* resid, const int* rowmap, int epi, const VitRope* vrope = nullptr) {
+    if (e->c.v_weight_dtype != 2) return gemm(e, s, A, lda, W, M, N, K, out, ldo, bias, resid, rowmap, epi);
+    if (A) SR_TRY(launch_quant_mx_act(s, A, lda, M, K, e->v_q8, e->v_qs, e->v_rows_pad));
+    GemmArgs a{reinterpret_cast<const bf16_t*>(e->v_q8), K, reinterpret_cast<const bf16_t*>(W8), M, N, K, out, ldo, bias, resid, rowmap, 1, w_scale, 256,
+               e->v_qs, e->v_rows_pad};
+    if (vrope) a.vrope = *vrope;
     SR_TRY(launch_gemm256_mx(s, a, epi));
     return 0;
 }
@@ -878,7 +946,8 @@ int sr_switches_reload(void) { load_switches(); return 0; }
 const char* sr_last_error(const sr_engine* e) { return e ? e->err : g_err; }
 
 size_t sr_workspace_bytes(const sr_config* cfg) {
-    if (!cfg || validate(*cfg)) return 0;
+    if (!cfg) return 0;
+    if (const char* why = validate(*cfg)) { (void)fail(nullptr, -22, "invalid sr_config: %s", why); return 0; }
     sr_engine tmp;
     tmp.c = *cfg;
     carve(&tmp);
@@ -923,6 +992,8 @@ int sr_engine_create(const sr_config* cfg, void* workspace, size_t workspace_byt
     if (r == hipSuccess) r = hipMemset(e->d_cur_tok, 0, (char*)e->d_tokens - (char*)e->d_cur_tok);
     if (r == hipSuccess) r = hipMemset(e->d_px, 0, 256 * sizeof(unsigned));
     if (r == hipSuccess) r = hipMemset(e->v_vt, 0, (size_t)e->c.v_hidden * e->v_vt_stride * sizeof(bf16_t));
+    // (the GEMM reads the scale rows of a whole 256-row tile: rows past the call's last stay valid e8m0 bytes, their products finite)
+    if (r == hipSuccess && e->v_qs) r = hipMemset(e->v_qs, 0, e->v_qs_bytes);
     // normalise LUT (hf image_transforms.py:89-124, 384-440) and rotary inverse frequencies (hf:506-523)
     std::vector<bf16_t> lut(768);
     const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, stdv[3] = {0.26862954f, 0.26130258f, 0.27577711f};
@@ -1005,21 +1076,21 @@ int sr_load_weight(sr_engine* e, const char* hf_name, const void* p, int dtype, 
         if (t == "norm1.weight") { dst = b.norm1; exp_rows = C; exp_cols = 1; }
         else if (t == "norm2.weight") { dst = b.norm2; exp_rows = C; exp_cols = 1; }
         // q / k channels of every head in paired order (vit_qk_perm): rotary partners 8 apart inside one 16-column tile
-        else if (t == "attn.qkv.weight") { dst = b.qkv_w; exp_rows = 3 * C; exp_cols = C; if (e->v_paired) { mode = 3; row_off = e->v_hd; } }
+        else if (t == "attn.qkv.weight") { dst = b.qkv_w; exp_rows = 3 * C; exp_cols = C; if (e->v_paired) { mode = 3; row_off = e->v_hd; } b.dirty[0] = 1; }
         else if (t == "attn.qkv.bias") { dst = b.qkv_b; exp_rows = 3 * C; exp_cols = 1; if (e->v_paired) { mode = 3; row_off = e->v_hd; } }
-        else if (t == "attn.proj.weight") { dst = b.proj_w; exp_rows = C; exp_cols = C; }
+        else if (t == "attn.proj.weight") { dst = b.proj_w; exp_rows = C; exp_cols = C; b.dirty[1] = 1; }
         else if (t == "attn.proj.bias") { dst = b.proj_b; exp_rows = C; exp_cols = 1; }
-        else if (t == "mlp.gate_proj.weight") { dst = b.gu_w; exp_rows = c.v_inter; exp_cols = C; mode = 1; }
+        else if (t == "mlp.gate_proj.weight") { dst = b.gu_w; exp_rows = c.v_inter; exp_cols = C; mode = 1; b.dirty[2] = 1; }
         else if (t == "mlp.gate_proj.bias") { dst = b.gu_b; exp_rows = c.v_inter; exp_cols = 1; mode = 1; }
-        else if (t == "mlp.up_proj.weight") { dst = b.gu_w; exp_rows = c.v_inter; exp_cols = C; mode = 2; }
+        else if (t == "mlp.up_proj.weight") { dst = b.gu_w; exp_rows = c.v_inter; exp_cols = C; mode = 2; b.dirty[2] = 1; }
         else if (t == "mlp.up_proj.bias") { dst = b.gu_b; exp_rows = c.v_inter; exp_cols = 1; mode = 2; }
-        else if (t == "mlp.down_proj.weight") { dst = b.down_w; exp_rows = C; exp_cols = c.v_inter; ld = e->v_inter_pad; }
+        else if (t == "mlp.down_proj.weight") { dst = b.down_w; exp_rows = C; exp_cols = c.v_inter; ld = e->v_inter_pad; b.dirty[3] = 1; }
         else if (t == "mlp.down_proj.bias") { dst = b.down_b; exp_rows = C; exp_cols = 1; }
     }
     else if (name == "visual.merger.ln_q.weight") { dst = e->ln_q; exp_rows = C; exp_cols = 1; }
-    else if (name == "visual.merger.mlp.0.weight") { dst = e->fc1_w; exp_rows = e->v_mh; exp_cols = e->v_mh; }
+    else if (name == "visual.merger.mlp.0.weight") { dst = e->fc1_w; exp_rows = e->v_mh; exp_cols = e->v_mh; e->fc_dirty[0] = 1; }
     else if (name == "visual.merger.mlp.0.bias") { dst = e->fc1_b; exp_rows = e->v_mh; exp_cols = 1; }
-    else if (name == "visual.merger.mlp.2.weight") { dst = e->fc2_w; exp_rows = c.v_out_hidden; exp_cols = e->v_mh; }
+    else if (name == "visual.merger.mlp.2.weight") { dst = e->fc2_w; exp_rows = c.v_out_hidden; exp_cols = e->v_mh; e->fc_dirty[1] = 1; }
     else if (name == "visual.merger.mlp.2.bias") { dst = e->fc2_b; exp_rows = c.v_out_hidden; exp_cols = 1; }
     else if (name == "model.embed_tokens.weight") { dst = e->embed; exp_rows = c.t_vocab; exp_cols = H; tiled = 1; }
     else if (name == "model.norm.weight") { dst = e->final_norm; exp_rows = H; exp_cols = 1; }
@@ -1085,12 +1156,21 @@ int sr_vit_forward(sr_engine* e, const void* pixels, int pixels_dtype, const int
     // patch embed (Conv3d k=s, no bias, hf:99-122) with the window permutation fused into the store (hf:433-441)
     if (int rc = gemm(e, s, pix, e->v_pd_pad, e->patch_w, N, C, e->v_pd_pad, e->v_x, C, nullptr, nullptr, e->v_rowmap_embed, EPI_STORE)) return rc;
     const float scale = (float)(1.0 / sqrt((double)hd));
+    const bool mx = c.v_weight_dtype == 2;      // fp8 x fp8 linears: every RMSNorm feeds only a GEMM, so it quantises in the same pass (v_xn is never written)
+    if (mx && !e->finalized) return fail(e, -22, "fp8 vision tower: call sr_finalize_weights after loading");
+    auto norm = [&](const bf16_t* nw, int group) {
+        return mx ? launch_rmsnorm_mx(s, e->v_x, nw, e->v_q8, e->v_qs, N, C, 1e-6f, group, e->v_rows_pad) : launch_rmsnorm(s, e->v_x, nw, e->v_xn, N, C, 1e-6f, 0, 1);
+    };
+    const bf16_t* xn = mx ? nullptr : e->v_xn;    // vit_gemm: null = the operand is already in v_q8 / v_qs
     for (int blk = 0; blk < c.v_depth; ++blk) {
         const VitBlockW& w = e->vb[blk];
-        SR_TRY(launch_rmsnorm(s, e->v_x, w.norm1, e->v_xn, N, C, 1e-6f, 0, 1));
+        SR_TRY(norm(w.norm1, 1));
         // qkv Linear; the 2-D rotary embedding and the V transpose ride in the GEMM epilogue when the 256-tile kernel takes the shape
         // (large batches; needs the paired q / k channel order the loader established), else they are the two launches of round 1
-        {
+        if (mx) {
+            const VitRope vr{e->v_cos, e->v_sin, e->v_vt, e->v_vt_stride, C, hd};
+            if (int rc = vit_gemm(e, s, nullptr, C, nullptr, w.qkv_w8, w.qkv_s, N, 3 * C, C, e->v_qkv, 3 * C, w.qkv_b, nullptr, nullptr, EPI_VITQKV, &vr)) return rc;
+        } else {
             GemmArgs ga{e->v_xn, C, w.qkv_w, N, 3 * C, C, e->v_qkv, 3 * C, w.qkv_b, nullptr, nullptr, 0, nullptr, 0};
             ga.vrope = VitRope{e->v_cos, e->v_sin, e->v_vt, e->v_vt_stride, C, hd};
             const bool fused = e->v_paired && gemm_fuses_vitqkv(ga);
@@ -1108,16 +1188,17 @@ int sr_vit_forward(sr_engine* e, const void* pixels, int pixels_dtype, const int
             if (attn_prefill_variant(a2, hd) == 2) a = a2;
         }
         SR_TRY(launch_attn_prefill(s, a, hd));
-        if (int rc = gemm(e, s, e->v_attn, C, w.proj_w, N, C, C, e->v_x, C, w.proj_b, e->v_x, nullptr, EPI_RESID)) return rc;
-        SR_TRY(launch_rmsnorm(s, e->v_x, w.norm2, e->v_xn, N, C, 1e-6f, 0, 1));
-        if (int rc = gemm(e, s, e->v_xn, C, w.gu_w, N, 2 * e->v_inter_pad, C, e->v_act, e->v_inter_pad, w.gu_b, nullptr, nullptr, EPI_SWIGLU)) return rc;
-        if (int rc = gemm(e, s, e->v_act, e->v_inter_pad, w.down_w, N, C, e->v_inter_pad, e->v_x, C, w.down_b, e->v_x, nullptr, EPI_RESID)) return rc;
+        if (int rc = vit_gemm(e, s, e->v_attn, C, w.proj_w, w.proj_w8, w.proj_s, N, C, C, e->v_x, C, w.proj_b, e->v_x, nullptr, EPI_RESID)) return rc;
+        SR_TRY(norm(w.norm2, 1));
+        if (int rc = vit_gemm(e, s, xn, C, w.gu_w, w.gu_w8, w.gu_s, N, 2 * e->v_inter_pad, C, e->v_act, e->v_inter_pad, w.gu_b, nullptr, nullptr, EPI_SWIGLU)) return rc;
+        if (int rc = vit_gemm(e, s, e->v_act, e->v_inter_pad, w.down_w, w.down_w8, w.down_s, N, C, e->v_inter_pad, e->v_x, C, w.down_b, e->v_x, nullptr, EPI_RESID)) return rc;
     }
-    // merger (hf:137-150) with the inverse window permutation fused into the last store (hf:463-465)
-    SR_TRY(launch_rmsnorm(s, e->v_x, e->ln_q, e->v_xn, N, C, 1e-6f, 0, 1));
-    const int T = N / (c.v_merge * c.v_merge);
-    if (int rc = gemm(e, s, e->v_xn, e->v_mh, e->fc1_w, T, e->v_mh, e->v_mh, e->v_m1, e->v_mh, e->fc1_b, nullptr, nullptr, EPI_GELU)) return rc;
-    if (int rc = gemm(e, s, e->v_m1, e->v_mh, e->fc2_w, T, c.v_out_hidden, e->v_mh, out, c.v_out_hidden, e->fc2_b, nullptr, e->v_rowmap_merge, EPI_STORE)) return rc;
+    // merger (hf:137-150) with the inverse window permutation fused into the last store (hf:463-465); ln_q normalises rows of C, mlp.0 sees
+    // merge^2 of them as one row
+    const int unit = c.v_merge * c.v_merge, T = N / unit;
+    SR_TRY(norm(e->ln_q, unit));
+    if (int rc = vit_gemm(e, s, xn, e->v_mh, e->fc1_w, e->fc1_w8, e->fc1_s, T, e->v_mh, e->v_mh, e->v_m1, e->v_mh, e->fc1_b, nullptr, nullptr, EPI_GELU)) return rc;
+    if (int rc = vit_gemm(e, s, e->v_m1, e->v_mh, e->fc2_w, e->fc2_w8, e->fc2_s, T, c.v_out_hidden, e->v_mh, out, c.v_out_hidden, e->fc2_b, nullptr, e->v_rowmap_merge, EPI_STORE)) return rc;
     return 0;
 }
 
@@ -1147,6 +1228,21 @@ int sr_finalize_weights(sr_engine* e, void* stream) {
             if (l.dirty[3]) SR_TRY(launch_quant_f8(s, l.down_w, H, e->t_inter_pad, l.down_w8, l.down_s));
             l.dirty[0] = l.dirty[1] = l.dirty[2] = l.dirty[3] = 0;
         }
+        SR_TRY((int)hipStreamSynchronize(s));
+    }
+    if (e->c.v_weight_dtype == 2) {
+        // the bf16 masters stay, so ANY reloaded tensor re-quantises its whole (fused) matrix from them: no partial-reload rule here
+        const int C = e->c.v_hidden, IP = e->v_inter_pad;
+        for (VitBlockW& b : e->vb) {
+            if (b.dirty[0]) SR_TRY(launch_quant_f8_rows(s, b.qkv_w, 3 * C, C, b.qkv_w8, b.qkv_s));
+            if (b.dirty[1]) SR_TRY(launch_quant_f8_rows(s, b.proj_w, C, C, b.proj_w8, b.proj_s));
+            if (b.dirty[2]) SR_TRY(launch_quant_f8_rows(s, b.gu_w, 2 * IP, C, b.gu_w8, b.gu_s));
+            if (b.dirty[3]) SR_TRY(launch_quant_f8_rows(s, b.down_w, C, IP, b.down_w8, b.down_s));
+            b.dirty[0] = b.dirty[1] = b.dirty[2] = b.dirty[3] = 0;
+        }
+        if (e->fc_dirty[0]) SR_TRY(launch_quant_f8_rows(s, e->fc1_w, e->v_mh, e->v_mh, e->fc1_w8, e->fc1_s));
+        if (e->fc_dirty[1]) SR_TRY(launch_quant_f8_rows(s, e->fc2_w, e->c.v_out_hidden, e->v_mh, e->fc2_w8, e->fc2_s));
+        e->fc_dirty[0] = e->fc_dirty[1] = 0;
         SR_TRY((int)hipStreamSynchronize(s));
     }
     e->finalized = true;
@@ -2040,6 +2136,20 @@ int sr_op_gemm_mx(const void* A8, int lda, const void* a_scale, int a_rows_pad, 
     GemmArgs a{(const bf16_t*)A8, lda, (const bf16_t*)W8, M, N, K, out, ldo, (const bf16_t*)bias, (const bf16_t*)resid, nullptr, 1, w_scale, 256,
                (const unsigned char*)a_scale, a_rows_pad};
     SR_WRAP(launch_gemm256_mx((hipStream_t)stream, a, epilogue & 0xff));
+}
+int sr_op_gemm_mx_vit(const void* A8, int lda, const void* a_scale, int a_rows_pad, const void* W8, const float* w_scale, int M, int N, int K, void* out,
+                      int ldo, const void* bias, const void* resid, const int32_t* rowmap, const float* cos_t, const float* sin_t, void* vt, int vt_stride,
+                      int head_dim, int epilogue, void* stream) {
+    GemmArgs a{(const bf16_t*)A8, lda, (const bf16_t*)W8, M, N, K, out, ldo, (const bf16_t*)bias, (const bf16_t*)resid, rowmap, 1, w_scale, 256,
+               (const unsigned char*)a_scale, a_rows_pad};
+    a.vrope = VitRope{cos_t, sin_t, (bf16_t*)vt, vt_stride, N / 3, head_dim};
+    SR_WRAP(launch_gemm256_mx((hipStream_t)stream, a, epilogue & 0xff));
+}
+int sr_op_rmsnorm_mx(const void* x, const void* w, void* q, void* scales, int rows, int C, int group, int rows_pad, float eps, void* stream) {
+    SR_WRAP(launch_rmsnorm_mx((hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)w, (unsigned char*)q, (unsigned char*)scales, rows, C, eps, group, rows_pad));
+}
+int sr_op_quant_f8_rows(const void* w, int N, int K, void* w8, float* scale, void* stream) {
+    SR_WRAP(launch_quant_f8_rows((hipStream_t)stream, (const bf16_t*)w, N, K, (unsigned char*)w8, scale));
 }
 int sr_op_gemv(const void* x, int ldx, const void* W, int M, int N, int K, void* out, int ksplit, int mode, void* stream) {
     GemvArgs a = gv((const bf16_t*)x, ldx, (const bf16_t*)W, M, N, K, out, (mode & 0xff) == GV_SWIGLU ? N / 2 : N);

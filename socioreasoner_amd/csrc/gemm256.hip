@@ -305,7 +305,7 @@ __global__ __launch_bounds__(512) void k_gemm256(GemmArgs p, int ntm, int ntn, i
         return uint4{sx[0], sy[0], sx[1], sy[1]};
     };
     if constexpr (EPI == EPI_VITQKV) {
-        // ViT qkv Linear with k_vit_rope + k_vit_vtranspose folded in.  The q / k channels of every head are in the paired order
+        // ViT qkv Linear with k_vit_rope + k_vit_vtranspose folded in (MX: the fp8 channel scale multiplies the accumulator first).  The q / k channels of every head are in the paired order
         // (vit_qk_perm): inside each 16-column tile columns 0..7 are x1 of 8 rotary pairs and 8..15 their x2, i.e. the partner of a
         // lane's 4 columns sits in lane ^ 32.  Sections (q | k | v, C columns each) start on tile boundaries: the role is block-uniform.
         const VitRope& f = p.vrope;
@@ -321,6 +321,7 @@ __global__ __launch_bounds__(512) void k_gemm256(GemmArgs p, int ntm, int ntn, i
                     const float4 c4 = rok[i] ? *reinterpret_cast<const float4*>(f.cos_t + (size_t)orow[i] * half + jl) : float4{0.f, 0.f, 0.f, 0.f};
                     const float4 s4 = rok[i] ? *reinterpret_cast<const float4*>(f.sin_t + (size_t)orow[i] * half + jl) : float4{0.f, 0.f, 0.f, 0.f};
                     float o[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+                    if constexpr (MX) { if (p.w_scale) { o[0] *= scl[j].x; o[1] *= scl[j].y; o[2] *= scl[j].z; o[3] *= scl[j].w; } }
                     if (p.bias) { o[0] += lo16(bia[j].x); o[1] += hi16(bia[j].x); o[2] += lo16(bia[j].y); o[3] += hi16(bia[j].y); }
                     const uint2 own = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};   // the Linear's bf16 output
                     const uint2 oth = uint2{(uint32_t)__shfl_xor((int)own.x, 32, 64), (uint32_t)__shfl_xor((int)own.y, 32, 64)};
@@ -354,6 +355,7 @@ __global__ __launch_bounds__(512) void k_gemm256(GemmArgs p, int ntm, int ntn, i
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         float o[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+                        if constexpr (MX) { if (p.w_scale) { o[0] *= scl[j].x; o[1] *= scl[j].y; o[2] *= scl[j].z; o[3] *= scl[j].w; } }
                         if (p.bias) { o[0] += lo16(bia[j].x); o[1] += hi16(bia[j].x); o[2] += lo16(bia[j].y); o[3] += hi16(bia[j].y); }
                         *reinterpret_cast<uint2*>(ex + (ii * 16 + fr) * EX_RS + (j * 16 + fg * 4) * 2) = uint2{pack2(o[0], o[1]), pack2(o[2], o[3])};
                     }
@@ -626,11 +628,12 @@ bool lmqkv_ok(const GemmArgs& a) {
 
 // fused ViT qkv epilogue: sections on tile boundaries, heads made of whole 16-column tiles, paired q / k channel order (the caller's
 // promise), V^T rows padded to the 8-row store granularity
-bool vitqkv_ok(const GemmArgs& a) {
+static bool vitqkv_layout_ok(const GemmArgs& a) {
     const VitRope& f = a.vrope;
     return f.cos_t && f.sin_t && f.vt && f.C > 0 && f.hd > 0 && f.C % BN2 == 0 && a.N == 3 * f.C && f.hd % 16 == 0 && f.C % f.hd == 0 &&
-           f.vt_stride % 8 == 0 && f.vt_stride >= (a.M + 7) / 8 * 8 && !a.rowmap && !a.w_scale && a.M % 4 == 0;
+           f.vt_stride % 8 == 0 && f.vt_stride >= (a.M + 7) / 8 * 8 && !a.rowmap;
 }
+bool vitqkv_ok(const GemmArgs& a) { return vitqkv_layout_ok(a) && !a.w_scale && a.M % 4 == 0; }
 
 // shapes the 256-tile kernel takes: whole 256-column tiles, at least two 64-wide k-tiles (M is arbitrary: edge rows are clamped
 // on load and masked on store)
@@ -645,6 +648,9 @@ int launch_gemm256_mx(hipStream_t s, const GemmArgs& a, int epi) {
         case EPI_SWIGLU: return launch256_t<EPI_SWIGLU, true>(s, a);
         case EPI_F32: return launch256_t<EPI_F32, true>(s, a);
         case EPI_LMQKV: return lmqkv_ok(a) ? launch256_t<EPI_LMQKV, true>(s, a) : -22;
+        // the vision tower's fp8 mode (v_weight_dtype 2): the merger's GELU, and the fused qkv epilogue -- at any row count, as every MX launch
+        case EPI_GELU: return launch256_t<EPI_GELU, true>(s, a);
+        case EPI_VITQKV: return vitqkv_layout_ok(a) ? launch256_t<EPI_VITQKV, true>(s, a) : -22;
     }
     return -22;
 }

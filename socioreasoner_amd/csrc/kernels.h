@@ -82,9 +82,12 @@ int gemm_prepare_decode();      // attribute calls of the tile kernels a decode 
 // gemm256.hip: 256 x 256 x 64 tile, 8-phase ping-pong schedule (large M); launch_gemm dispatches to it
 bool gemm256_supports(const GemmArgs& a);
 int launch_gemm256(hipStream_t s, const GemmArgs& a, int epi);
-int launch_gemm256_mx(hipStream_t s, const GemmArgs& a, int epi);
+int launch_gemm256_mx(hipStream_t s, const GemmArgs& a, int epi);      // STORE / RESID / SWIGLU / GELU / F32 / LMQKV / VITQKV; honours rowmap
 // MX activation quantiser (OCP MX, e4m3 elements, 32-wide blocks): x bf16 [M][ldx] -> q fp8 [M][K] + e8m0 scales [K/128][rows_pad][4]
 int launch_quant_mx_act(hipStream_t s, const bf16_t* x, int ldx, int M, int K, unsigned char* q, unsigned char* scales, int rows_pad);
+// per-row RMSNorm (the wave-per-row form of launch_rmsnorm) fused with the MX quantiser: the bytes of launch_rmsnorm(per_wave) followed by
+// launch_quant_mx_act on the [rows / group][group * H] view (group consecutive normalised rows = one GEMM row); H % 128 == 0
+int launch_rmsnorm_mx(hipStream_t s, const bf16_t* x, const bf16_t* w, unsigned char* q, unsigned char* scales, int rows, int H, float eps, int group, int rows_pad);
 
 // ------------------------------------------------------------------ gemv.hip (weight streaming, M <= 32)
 enum { GV_PARTIAL = 0, GV_SWIGLU = 1, GV_F32 = 2, GV_BIAS = 3, GV_RESID = 4 };
@@ -212,6 +215,8 @@ struct StepArgs {
 // fp8 quantisation of a fragment-ordered bf16 matrix [N, K]: scale[n] = amax_n / 448 (1 if the row is zero),
 // q = fp8(W / scale) -> W8 (tiled8); W itself is overwritten with q as bf16 (what the prefill GEMM multiplies, scaled in its epilogue)
 int launch_quant_f8(hipStream_t s, bf16_t* W_tiled, int N, int K, unsigned char* W8, float* scale);
+// the same quantisation of a ROW-MAJOR bf16 matrix [N][K] (K % 128 == 0), which is left as it is: W8 = tiled8 image, scale [N]
+int launch_quant_f8_rows(hipStream_t s, const bf16_t* W, int N, int K, unsigned char* W8, float* scale);
 int launch_step(hipStream_t s, const StepArgs& a);
 // one row's sampling parameters.  inv_temp 0 = greedy (run as top_k = 1: the lowest id among the maxima of the penalised logits); top_k <= 0 or
 // >= V = no top-k bound (k_sample_full).  The draw for step s uses the key (seed, stream, s); stream RP_ROW_STREAM = the draw's own index b

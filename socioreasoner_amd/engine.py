@@ -9,10 +9,10 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .config import ModelGeometry
+from .config import ModelGeometry, check_supported
 
 
-def _sr_config(g: ModelGeometry, max_patches, max_prefill_tokens, max_batch, max_ctx, max_new_tokens, lm_fp8=False, kv_slots=0) -> L.SrConfig:
+def _sr_config(g: ModelGeometry, max_patches, max_prefill_tokens, max_batch, max_ctx, max_new_tokens, lm_fp8=False, kv_slots=0, vit_fp8=False) -> L.SrConfig:
     v, t = g.vision, g.text
     c = L.SrConfig()
     c.v_depth, c.v_hidden, c.v_heads, c.v_inter = v.depth, v.hidden_size, v.num_heads, v.intermediate_size
@@ -31,21 +31,27 @@ def _sr_config(g: ModelGeometry, max_patches, max_prefill_tokens, max_batch, max
     c.max_ctx, c.max_new_tokens = max_ctx, max_new_tokens
     c.kv_slots = int(kv_slots)
     c.lm_weight_dtype = 2 if lm_fp8 == "mx" else 1 if lm_fp8 else 0      # "mx": fp8 weights + MX fp8 activations in prefill (fp8 x fp8 MFMA)
+    if vit_fp8 not in (False, None, "mx"):
+        raise ValueError(f"vit_fp8={vit_fp8!r}: False (bf16 vision tower) or 'mx' (fp8 weights x MX fp8 activations, sr_config.v_weight_dtype = 2)")
+    c.v_weight_dtype = 2 if vit_fp8 == "mx" else 0
     return c
 
 
 class Engine:
     def __init__(self, geometry: ModelGeometry, *, max_patches=1024, max_prefill_tokens=512, max_batch=1, max_ctx=640,
-                 max_new_tokens=128, device="cuda:0", lm_fp8=False, kv_slots: int = 0):
-        """kv_slots: KV-cache slots (0 = max_batch); spare slots let the scheduler prefill the next requests while all rows decode"""
+                 max_new_tokens=128, device="cuda:0", lm_fp8=False, kv_slots: int = 0, vit_fp8=False):
+        """kv_slots: KV-cache slots (0 = max_batch); spare slots let the scheduler prefill the next requests while all rows decode.
+        vit_fp8: False = bf16 vision tower; "mx" = its linears fp8 x fp8 on the block-scaled MFMA (sr_config.v_weight_dtype = 2), independent of lm_fp8"""
         self.lib = L.load()
         self.lib_held = L.load_held()          # the scheduler's queue-only calls, made without releasing the interpreter lock (lib.load_held)
         if not torch.cuda.is_available():
             raise L.SocioRError("no GPU visible: the product path has no CPU fallback")
         self.geom = geometry
+        if vit_fp8:
+            check_supported(geometry, vit_fp8=vit_fp8)
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
-        self.cfg = _sr_config(geometry, max_patches, max_prefill_tokens, max_batch, max_ctx, max_new_tokens, lm_fp8, kv_slots)
+        self.cfg = _sr_config(geometry, max_patches, max_prefill_tokens, max_batch, max_ctx, max_new_tokens, lm_fp8, kv_slots, vit_fp8)
         self.kv_slots = int(kv_slots) or int(max_batch)
         nbytes = self.lib.sr_workspace_bytes(C.byref(self.cfg))
         if nbytes == 0:

@@ -20,6 +20,7 @@ class SrConfig(C.Structure):
         ("image_token_id", C.c_int32),
         ("max_patches", C.c_int32), ("max_prefill_tokens", C.c_int32), ("max_batch", C.c_int32),
         ("max_ctx", C.c_int32), ("max_new_tokens", C.c_int32), ("lm_weight_dtype", C.c_int32), ("kv_slots", C.c_int32),
+        ("v_weight_dtype", C.c_int32),
     ]
 
 
@@ -75,6 +76,9 @@ SIGNATURES = {
     "sr_op_gemm": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "sr_op_quant_mx": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "sr_op_gemm_mx": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
+    "sr_op_rmsnorm_mx": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_float, _vp]),
+    "sr_op_gemm_mx_vit": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sr_op_quant_f8_rows": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp]),
     "sr_op_gemv": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
     "sr_op_gemv_fused": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _vp, _vp]),
     "sr_op_gemv_f32_blocks": (C.c_int, [_i, _i, _i, _i]),
