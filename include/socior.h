@@ -277,6 +277,19 @@ int sr_rows_set_cus(sr_engine* e, int n_cus, void* stream);
  * rlvr_socioseg_vlm_pipeline_infer.py:45-58 (IoU counts) and :383-452 (render).  No engine needed. */
 int sr_mask_union(uint8_t* dev_acc, const uint8_t* dev_mask, size_t n, void* stream);
 int sr_resize_nearest_u8(const uint8_t* dev_src, int sh, int sw, uint8_t* dev_dst, int dh, int dw, void* stream);
+/* PIL's Image.resize of 8-bit images (BICUBIC / BILINEAR / LANCZOS), bit for bit -- replaces the host resize in front of the ViT and of SAM2
+ * (rlvr_socioseg_vlm_pipeline_infer.py:126-144, seg_strategy.py:44).  n_img equally sized images, contiguous: dev_src [n_img][sh][sw][channels] ->
+ * dev_dst [n_img][dh][dw][channels]; any byte alignment.  The horizontal pass (skipped when sw == dw) runs over every source row, the vertical
+ * pass (skipped when sh == dh) on its uint8 result in dev_tmp; with both sizes equal the call is a device-to-device copy.  One launch per pass.
+ *   dev_kk_h [dw][ksize_h], dev_bounds_h [dw][2], dev_kk_v [dh][ksize_v], dev_bounds_v [dh][2]: the 22-bit fixed-point taps and (first source
+ *     index, tap count) of each output index, as socioreasoner_amd/hostops.py pil_resample_coeffs(sw, dw, filter) / (sh, dh, filter) builds
+ *     them.  Preconditions (not checked): first >= 0, first + count <= the source size, count <= ksize, both non-decreasing in the output index.
+ *   dev_tmp: n_img * sh * dw * channels bytes; may be NULL when at most one pass runs.  dev_src, dev_dst and dev_tmp do not overlap.
+ * Returns -22 and launches nothing for: channels not 1 or 3 (PIL resizes RGBA through a premultiplied copy), a side outside 1 .. 8192,
+ * n_img < 1, a missing table of a pass that runs, a missing dev_tmp when both passes run. */
+int sr_resize_pil_u8(const uint8_t* dev_src, int sh, int sw, uint8_t* dev_dst, int dh, int dw, int channels, int n_img,
+                     const int32_t* dev_kk_h, const int32_t* dev_bounds_h, int ksize_h,
+                     const int32_t* dev_kk_v, const int32_t* dev_bounds_v, int ksize_v, uint8_t* dev_tmp, void* stream);
 int sr_iou_counts(const uint8_t* dev_pred, const uint8_t* dev_gt, size_t n, int64_t* dev_out2, void* stream);
 /* the same counts for n_items (prediction, ground truth) pairs of n bytes each, stored back to back, in ONE launch: dev_out [n_items][2] */
 int sr_iou_counts_batched(const uint8_t* dev_pred, const uint8_t* dev_gt, size_t n, int n_items, int64_t* dev_out, void* stream);

@@ -43,6 +43,11 @@ class _StubTokenizer:
         return [" ".join(str(int(t)) for t in row if not (skip_special_tokens and int(t) == self.pad_token_id)) for row in ids]
 
 
+# strategy_config device_resize when unset.  The rule: true once tools/bench_resize.py has shown, on an MI355X, the device path (upload at the source
+# size + sr_resize_pil_u8) faster than the host path (PIL + upload) by more than the measured spread (profiles/device_resize.json); until then false.
+DEVICE_RESIZE_DEFAULT = False
+
+
 def _get(obj, name, default=None):
     if obj is None:
         return default
@@ -264,6 +269,15 @@ class Mi355xStrategy(InferenceStrategy):
         return collate_fn_to_dict_list(results)
 
     # ------------------------------------------------------------------ generate
+    def _device_resize(self) -> bool:
+        """strategy_config device_resize (default DEVICE_RESIZE_DEFAULT): a host image of a size the ViT cannot take is uploaded as it is and resized by
+        sr_resize_pil_u8 (PIL's bicubic, bit for bit) instead of by PIL on the calling thread; false = the host resize."""
+        v = self.__dict__.get("device_resize")
+        if v is None:
+            sc = _get(_get(getattr(self, "worker_config", None), "strategy_args"), "strategy_config", None) or {}
+            v = self.device_resize = bool(dict(sc).get("device_resize", DEVICE_RESIZE_DEFAULT))
+        return v
+
     def _prepare(self, ids: List[int], images, side_stream: bool = False) -> tuple:
         """-> (expanded ids np.int64, pos3 [3,S], list of uint8 HWC cuda images, grids).  side_stream: host images are uploaded on a stream of their
         own instead of the caller's current (usually the null) stream -- next to a running request loop a null-stream copy would wait for everything the
@@ -284,15 +298,29 @@ class Mi355xStrategy(InferenceStrategy):
                     ims.append(im.contiguous())
                     grids.append((1, rh // g.vision.patch_size, rw // g.vision.patch_size))
                     continue
-                im = im.cpu().numpy()                            # a size the ViT cannot take: bicubic resize on the host
+                if im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3:
+                    # a size the ViT cannot take: PIL's bicubic resize as a kernel on the caller's stream, where the image lives (sr_resize_pil_u8;
+                    # it replaces a copy to the host, the host resize and the upload, whatever device_resize says)
+                    ims.append(raster.resize_pil(im, rh, rw, "bicubic"))
+                    grids.append((1, rh // g.vision.patch_size, rw // g.vision.patch_size))
+                    continue
+                im = im.cpu().numpy()                            # (not uint8 RGB: bicubic resize on the host)
             arr = np.asarray(im.convert("RGB")) if hasattr(im, "convert") else np.asarray(im)
             h, w = arr.shape[:2]
             rh, rw = hostops.smart_resize(h, w, factor=f)
-            if (rh, rw) != (h, w):
+            on_device = (rh, rw) != (h, w) and self._device_resize() and arr.dtype == np.uint8 and arr.ndim == 3 and arr.shape[2] == 3
+            if (rh, rw) != (h, w) and not on_device:
                 from PIL import Image
                 arr = np.asarray(Image.fromarray(arr).resize((rw, rh), resample=Image.BICUBIC))
             with up:
-                ims.append(torch.from_numpy(np.array(arr, dtype=np.uint8, order="C")).cuda())
+                t = torch.from_numpy(np.array(arr, dtype=np.uint8, order="C")).cuda()
+                if on_device:
+                    # uploaded at its own size, resized on the stream of the upload.  The pageable copy is synchronous for the host, the kernel is
+                    # not: the image is handed on only after its stream has drained (a wait of microseconds), which is all the ordering the
+                    # request loop has with the upload stream
+                    t = raster.resize_pil(t, rh, rw, "bicubic")
+                    torch.cuda.current_stream(t.device).synchronize()
+                ims.append(t)
             grids.append((1, rh // g.vision.patch_size, rw // g.vision.patch_size))
         ids = np.asarray(ids, dtype=np.int64)
         n_pad = int((ids == g.image_token_id).sum())
@@ -673,7 +701,8 @@ class SegRasterStrategy(InferenceStrategy):
 
     def _resized(self, image):
         """image.resize((756, 756)) (seg_strategy.py:44), remembered per image OBJECT: the second stage segments the image the first stage did
-        (3.7 ms of PIL bicubic per call)."""
+        (3.7 ms of PIL bicubic per call).  The host path: with strategy_config device_resize on and a predictor that takes
+        ``resize_to`` the original images go to the device and neither this method nor its memo is used (`_resize_on_device`)."""
         from collections import OrderedDict
         import threading
         memo = self.__dict__.setdefault("_r756", OrderedDict())
@@ -690,11 +719,33 @@ class SegRasterStrategy(InferenceStrategy):
                 memo.popitem(last=False)
         return r
 
+    _device_resize = Mi355xStrategy._device_resize      # strategy_config device_resize
+
+    def _resize_on_device(self, images) -> bool:
+        """True when the predictor resizes on the device (socioreasoner_amd.sam2.Sam2Predictor: ``resize_to``) and the switch is on: the ORIGINAL
+        images go in, neither `_resized` nor its memo is used.  Images that are not plain RGB (PIL converts after the resize there, the device path
+        before it) keep the host path."""
+        import inspect
+        fn = getattr(self.model, "segment_batch", None)
+        if fn is None or not self._device_resize():
+            return False
+        try:
+            if "resize_to" not in inspect.signature(fn).parameters:
+                return False
+        except (TypeError, ValueError):
+            return False
+        return all(getattr(im, "mode", "RGB") == "RGB" and (hasattr(im, "mode") or (getattr(im, "ndim", 0) == 3 and im.shape[2] == 3 and str(im.dtype).endswith("uint8")))
+                   for im in images)
+
     def prefetch(self, images, chunk=None) -> None:
         """Round 6: start SAM2's image encoder on these images in the background (socioreasoner_amd.sam2.Sam2Predictor.prefetch); `segment` later finds
         the embeddings cached.  Predictors without `prefetch` (the reference's SAM2ImagePredictor) ignore the hint."""
         if self.model is not None and hasattr(self.model, "prefetch"):
-            self.model.prefetch(list(images), prepare=self._resized, chunk=chunk)      # (the 756 x 756 resize, 3.7 ms per image, on the prefetch thread as well)
+            images = list(images)
+            if self._resize_on_device(images):
+                self.model.prefetch(images, chunk=chunk, resize_to=(756, 756))      # (the 756 x 756 resize is a kernel on the upload stream)
+                return
+            self.model.prefetch(images, prepare=self._resized, chunk=chunk)      # (the 756 x 756 resize, 3.7 ms per image, on the prefetch thread as well)
 
     def wait_prefetch(self) -> None:
         if self.model is not None and hasattr(self.model, "wait_prefetch"):
@@ -712,7 +763,10 @@ class SegRasterStrategy(InferenceStrategy):
         if live and hasattr(self.model, "segment_batch"):
             # socioreasoner_amd.sam2: the encoder runs over several images per pass (and not at all for an image it has seen: stage 2
             # segments stage 1's image), decode / arg-max / resize / threshold / OR stay on the device
-            accs = self.model.segment_batch([self._resized(images[i]) for i in live], [prompts[i] for i in live])
+            if self._resize_on_device([images[i] for i in live]):
+                accs = self.model.segment_batch([images[i] for i in live], [prompts[i] for i in live], resize_to=(756, 756))
+            else:
+                accs = self.model.segment_batch([self._resized(images[i]) for i in live], [prompts[i] for i in live])
             for i, acc in zip(live, accs):
                 masks[i] = raster.resize_nearest(acc, 768, 768).cpu().numpy()
             live = []

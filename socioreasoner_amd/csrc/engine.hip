@@ -2024,6 +2024,10 @@ int sr_mask_union(uint8_t* acc, const uint8_t* m, size_t n, void* stream) { SR_W
 int sr_resize_nearest_u8(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, void* stream) {
     SR_WRAP(launch_resize_nearest_u8((hipStream_t)stream, src, sh, sw, dst, dh, dw));
 }
+int sr_resize_pil_u8(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, int channels, int n_img, const int32_t* kk_h,
+                     const int32_t* bounds_h, int ksize_h, const int32_t* kk_v, const int32_t* bounds_v, int ksize_v, uint8_t* tmp, void* stream) {
+    SR_WRAP(launch_resize_pil_u8((hipStream_t)stream, src, sh, sw, dst, dh, dw, channels, n_img, kk_h, bounds_h, ksize_h, kk_v, bounds_v, ksize_v, tmp));
+}
 int sr_iou_counts(const uint8_t* p, const uint8_t* g, size_t n, int64_t* out2, void* stream) {
     SR_WRAP(launch_iou_counts((hipStream_t)stream, p, g, n, reinterpret_cast<long long*>(out2)));
 }

@@ -134,6 +134,100 @@ __global__ __launch_bounds__(256) void k_render(uint8_t* img, int h, int w, cons
     px[0] = (uint8_t)c0; px[1] = (uint8_t)c1; px[2] = (uint8_t)c2;
 }
 
+// ---- PIL's 8-bit resampling (Image.resize with BICUBIC / BILINEAR / LANCZOS), bit for bit: Pillow computes the taps of an axis once in double
+// precision, rounds them to 22-bit fixed point and runs two separable integer passes with a uint8 intermediate.  The tables come from the host
+// (socioreasoner_amd/hostops.py pil_resample_coeffs): kk [out][ksize] int32, bounds [out][2] = (first source index, number of taps).  Both passes
+// accumulate in int32 like Pillow (sum |taps| < 1.4 * 2^22, times 255 < 2^31) and are integer VALU only, bound by memory.
+constexpr int RS_BITS = 22;
+constexpr int RS_RUN = 256;                  // output pixels of one horizontal block = its threads
+constexpr int RS_LDS_BYTES = 16384;          // source bytes of a run staged in LDS (768 -> 756 RGB: 0.8 KB; a run that spans more reads global memory directly)
+
+__device__ __forceinline__ uint32_t rs_clip8(int s) { return (uint32_t)min(max(s >> RS_BITS, 0), 255); }
+
+// Horizontal pass: block = (one source row, RS_RUN adjacent output pixels).  xmin and xmin + xmax grow with the output index, so the bytes the run
+// reads are [bounds[first].xmin, bounds[last].xmin + bounds[last].xmax) * C: loaded as ALIGNED dwords (the row starts at any byte address; an aligned
+// dword that holds one byte of the image lies in that byte's page, so the up to 3 bytes read before / after the span cannot fault and are never used).
+template <int C>
+__global__ __launch_bounds__(RS_RUN) void k_resample_h(const uint8_t* __restrict__ src, int sw, uint8_t* __restrict__ dst, int dw, int n_runs,
+                                                        const int* __restrict__ kk, const int* __restrict__ bounds, int ksize) {
+    __shared__ uint32_t lds[RS_LDS_BYTES / 4 + 1];
+    const size_t row = blockIdx.x / (unsigned)n_runs;
+    const int x0 = (int)(blockIdx.x % (unsigned)n_runs) * RS_RUN, x1 = min(x0 + RS_RUN, dw) - 1;
+    const int first = bounds[2 * x0], last = bounds[2 * x1] + bounds[2 * x1 + 1];
+    const uint8_t* in = src + row * (size_t)sw * C + (size_t)first * C;
+    const int span = (last - first) * C, skew = (int)(reinterpret_cast<uintptr_t>(in) & 3);
+    const bool staged = span + skew <= RS_LDS_BYTES;          // uniform over the block
+    if (staged) {
+        const uint32_t* in4 = reinterpret_cast<const uint32_t*>(in - skew);
+        for (int i = threadIdx.x; i < (span + skew + 3) / 4; i += RS_RUN) lds[i] = in4[i];
+        __syncthreads();
+    }
+    const int xx = x0 + threadIdx.x;
+    if (xx > x1) return;
+    const int xmin = bounds[2 * xx], xmax = bounds[2 * xx + 1];
+    const int* k = kk + (size_t)xx * ksize;
+    int acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = 1 << (RS_BITS - 1);
+    if (staged) {
+        const uint8_t* p = reinterpret_cast<const uint8_t*>(lds) + skew + (xmin - first) * C;
+        for (int t = 0; t < xmax; ++t) {
+            const int w = k[t];
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] += w * (int)p[t * C + c];
+        }
+    } else {
+        const uint8_t* p = in + (size_t)(xmin - first) * C;
+        for (int t = 0; t < xmax; ++t) {
+            const int w = k[t];
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] += w * (int)p[(size_t)t * C + c];
+        }
+    }
+    uint8_t* o = dst + (row * (size_t)dw + xx) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = (uint8_t)rs_clip8(acc[c]);
+}
+
+// Vertical pass: the taps depend on neither x nor the channel, so a row is a flat vector of wb = W * C bytes.  Block = (one output row, 256 pieces of
+// it); piece 0 is the up to 3 bytes in front of the row's first dword-aligned address, every other piece 4 bytes from there on, the last one cut at
+// the row's end.  A whole piece is one aligned dword store fed by one dword load per source row (those are aligned only where wb % 4 == 0: memcpy
+// leaves the access width to the compiler); head and tail pieces go byte by byte.
+__device__ __forceinline__ uint32_t rs_load4(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+
+__global__ __launch_bounds__(256) void k_resample_v(const uint8_t* __restrict__ src, int sh, uint8_t* __restrict__ dst, int dh, int wb, int n_chunks,
+                                                     const int* __restrict__ kk, const int* __restrict__ bounds, int ksize) {
+    const size_t orow = blockIdx.x / (unsigned)n_chunks;          // image * dh + yy
+    const int yy = (int)(orow % (unsigned)dh);
+    const size_t img = orow / (unsigned)dh;
+    uint8_t* out = dst + orow * (size_t)wb;
+    const int head = (int)((4 - (reinterpret_cast<uintptr_t>(out) & 3)) & 3);
+    const int piece = (int)(blockIdx.x % (unsigned)n_chunks) * 256 + threadIdx.x;
+    const int lo = piece == 0 ? 0 : min(head + 4 * (piece - 1), wb), hi = min(head + 4 * piece, wb);
+    if (lo >= hi) return;
+    const int ymin = bounds[2 * yy], ymax = bounds[2 * yy + 1];
+    const int* k = kk + (size_t)yy * ksize;
+    const uint8_t* in = src + (img * (size_t)sh + ymin) * (size_t)wb + lo;
+    if (hi - lo == 4 && piece > 0) {
+        int a0 = 1 << (RS_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
+        for (int t = 0; t < ymax; ++t) {
+            const int w = k[t];
+            const uint32_t v = rs_load4(in + (size_t)t * wb);
+            a0 += w * (int)(v & 255u);
+            a1 += w * (int)((v >> 8) & 255u);
+            a2 += w * (int)((v >> 16) & 255u);
+            a3 += w * (int)(v >> 24);
+        }
+        *reinterpret_cast<uint32_t*>(out + lo) = rs_clip8(a0) | (rs_clip8(a1) << 8) | (rs_clip8(a2) << 16) | (rs_clip8(a3) << 24);
+        return;
+    }
+    for (int b = 0; b < hi - lo; ++b) {
+        int a = 1 << (RS_BITS - 1);
+        for (int t = 0; t < ymax; ++t) a += k[t] * (int)in[(size_t)t * wb + b];
+        out[lo + b] = (uint8_t)rs_clip8(a);
+    }
+}
+
 }  // namespace
 
 int launch_mask_union(hipStream_t s, uint8_t* acc, const uint8_t* m, size_t n) {
@@ -179,5 +273,33 @@ int launch_render_overlay(hipStream_t s, uint8_t* img, int h, int w, const uint8
     if (h <= 0 || w <= 0) return 0;
     hipLaunchKernelGGL(k_render, dim3(cdiv(w, 256), h), dim3(256), 0, s, img, h, w, mask, mh, mw, boxes, nb);
     SR_CHECK_LAUNCH();
+    return 0;
+}
+
+// Image.resize of n_img equally sized, contiguous uint8 images [sh][sw][C] -> [dh][dw][C]: the horizontal pass over every source row (into tmp when a
+// vertical pass follows), then the vertical pass on its uint8 result; a pass whose two sizes are equal is skipped.  One launch per pass for the batch.
+int launch_resize_pil_u8(hipStream_t s, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, int C, int n_img, const int* kk_h,
+                         const int* bounds_h, int ksize_h, const int* kk_v, const int* bounds_v, int ksize_v, uint8_t* tmp) {
+    const bool need_h = sw != dw, need_v = sh != dh;
+    if ((C != 1 && C != 3) || n_img < 1 || !src || !dst) return -22;
+    if (sh < 1 || sh > 8192 || sw < 1 || sw > 8192 || dh < 1 || dh > 8192 || dw < 1 || dw > 8192) return -22;
+    if (need_h && (!kk_h || !bounds_h || ksize_h < 1)) return -22;
+    if (need_v && (!kk_v || !bounds_v || ksize_v < 1)) return -22;
+    if (need_h && need_v && !tmp) return -22;
+    const int n_runs = cdiv(dw, RS_RUN), wb = dw * C, n_chunks = cdiv(cdiv(wb, 4) + 1, 256);
+    if ((need_h && (size_t)n_img * sh * n_runs > 0x7fffffffull) || (need_v && (size_t)n_img * dh * n_chunks > 0x7fffffffull)) return -22;      // grid x
+    if (!need_h && !need_v) return (int)hipMemcpyAsync(dst, src, (size_t)n_img * sh * sw * C, hipMemcpyDeviceToDevice, s);
+    if (need_h) {
+        uint8_t* out = need_v ? tmp : dst;
+        const dim3 grid((unsigned)((size_t)n_img * sh * n_runs));
+        if (C == 3) hipLaunchKernelGGL(k_resample_h<3>, grid, dim3(RS_RUN), 0, s, src, sw, out, dw, n_runs, kk_h, bounds_h, ksize_h);
+        else hipLaunchKernelGGL(k_resample_h<1>, grid, dim3(RS_RUN), 0, s, src, sw, out, dw, n_runs, kk_h, bounds_h, ksize_h);
+        SR_CHECK_LAUNCH();
+    }
+    if (need_v) {
+        hipLaunchKernelGGL(k_resample_v, dim3((unsigned)((size_t)n_img * dh * n_chunks)), dim3(256), 0, s, need_h ? tmp : src, sh, dst, dh, wb, n_chunks,
+                           kk_v, bounds_v, ksize_v);
+        SR_CHECK_LAUNCH();
+    }
     return 0;
 }

@@ -254,3 +254,107 @@ def get_dist_info_from_comm_plan(comm_plan: Dict[Any, Dict[str, Any]], rank_in_c
             if tgt["rank"] == rank_in_cluster and tgt["device"]["rank"] == rank_in_worker:
                 return pos, args
     return None, None
+
+
+# ---------------------------------------------------------------------------------------------------- PIL's 8-bit resampling, restated
+# Pillow's ImagingResample for 8-bit images (src/libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc,
+# ImagingResampleHorizontal_8bpc / ImagingResampleVertical_8bpc): per axis the filter taps are computed once in double precision and
+# rounded to 22-bit fixed point; the pixels then go through two separable integer passes with a uint8 intermediate.  Nothing in it is
+# floating-point image processing, so it can be restated bit for bit; raster.resize_pil runs the same passes on the device from the
+# tables built here.
+PIL_PRECISION_BITS = 22
+
+
+def _pil_bicubic(x: float) -> float:
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _pil_bilinear(x: float) -> float:
+    if x < 0.0:
+        x = -x
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _pil_sinc(x: float) -> float:
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _pil_lanczos(x: float) -> float:
+    return _pil_sinc(x) * _pil_sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+PIL_FILTERS = {"bicubic": (_pil_bicubic, 2.0), "bilinear": (_pil_bilinear, 1.0), "lanczos": (_pil_lanczos, 3.0)}      # name -> (kernel, support)
+
+
+def pil_resample_coeffs(in_size: int, out_size: int, filter: str = "bicubic"):
+    """The taps of one axis -> (kk int32 [out_size, ksize], bounds int32 [out_size, 2] = (xmin, xmax)): output index xx is
+    clip8((sum_{k < xmax} kk[xx, k] * src[xmin + k] + 2**21) >> 22).  Python doubles in Pillow's operation order (the sum ``ww`` in index order;
+    the argument of the filter is scaled by the reciprocal ``1 / filterscale`` like Pillow's ``ss``, which equals the division for every
+    upscale and is what the bit-for-bit comparison with PIL holds for downscales); unused taps are 0."""
+    if filter not in PIL_FILTERS:
+        raise ValueError(f"filter {filter!r}: one of {sorted(PIL_FILTERS)}")
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"in_size {in_size} / out_size {out_size}: both must be >= 1")
+    fn, fsupport = PIL_FILTERS[filter]
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = fsupport * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    one = float(1 << PIL_PRECISION_BITS)
+    kk = np.zeros((out_size, ksize), dtype=np.int32)
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [fn((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        for x, v in enumerate(w):
+            kk[xx, x] = int(v * one - 0.5) if v < 0 else int(v * one + 0.5)
+        bounds[xx] = (xmin, xmax)
+    return kk, bounds
+
+
+def _pil_pass(src: np.ndarray, kk: np.ndarray, bounds: np.ndarray, axis: int) -> np.ndarray:
+    """One integer pass along `axis` (0 = vertical, 1 = horizontal) of a uint8 [h, w, c] array."""
+    a = np.moveaxis(src, axis, 0).astype(np.int64)
+    out = np.empty((kk.shape[0],) + a.shape[1:], dtype=np.uint8)
+    for xx in range(kk.shape[0]):
+        xmin, xmax = int(bounds[xx, 0]), int(bounds[xx, 1])
+        s = np.tensordot(kk[xx, :xmax].astype(np.int64), a[xmin:xmin + xmax], axes=(0, 0)) + (1 << (PIL_PRECISION_BITS - 1))
+        out[xx] = np.clip(s >> PIL_PRECISION_BITS, 0, 255)          # (>> on int64 is arithmetic)
+    return np.moveaxis(out, 0, axis)
+
+
+def pil_resize_ref(arr_u8_hwc: np.ndarray, out_h: int, out_w: int, filter: str = "bicubic") -> np.ndarray:
+    """``Image.fromarray(arr).resize((out_w, out_h), resample=filter)`` of a uint8 [h, w] or [h, w, 3] array, bit for bit: the horizontal pass
+    over every input row first (skipped when the widths are equal), then the vertical pass on its uint8 result (skipped when the heights are
+    equal).  4 channels are refused: PIL resizes RGBA through a premultiplied copy."""
+    arr = np.asarray(arr_u8_hwc)
+    if arr.dtype != np.uint8:
+        raise ValueError(f"arr_u8_hwc: dtype {arr.dtype}, uint8 expected")
+    if arr.ndim not in (2, 3) or (arr.ndim == 3 and arr.shape[2] not in (1, 3)):
+        raise ValueError(f"arr_u8_hwc: shape {arr.shape}, [h, w] or [h, w, 3] expected (4 channels: PIL premultiplies RGBA, not restated here)")
+    out = arr.reshape(arr.shape[0], arr.shape[1], -1)
+    h, w = out.shape[:2]
+    if int(out_w) != w:
+        out = _pil_pass(out, *pil_resample_coeffs(w, out_w, filter), axis=1)
+    if int(out_h) != h:
+        out = _pil_pass(out, *pil_resample_coeffs(h, out_h, filter), axis=0)
+    return np.ascontiguousarray(out.reshape((int(out_h), int(out_w)) + arr.shape[2:]))

@@ -4,9 +4,12 @@ Reference behaviour: /root/reference/roll/distributed/strategy/seg_strategy.py:3
 from __future__ import annotations
 
 import ctypes as C
+import threading
+from collections import OrderedDict
 
 import torch
 
+from . import hostops
 from . import lib as L
 
 
@@ -29,6 +32,63 @@ def resize_nearest(src: torch.Tensor, H: int, W: int) -> torch.Tensor:
     L.check(L.load().sr_resize_nearest_u8(C.c_void_p(src.data_ptr()), src.shape[0], src.shape[1], C.c_void_p(dst.data_ptr()), H, W, _s(src)),
             None, "sr_resize_nearest_u8")
     return dst
+
+
+_RS_TABLES: "OrderedDict[tuple, tuple]" = OrderedDict()      # (in, out, filter, device) -> (kk, bounds, ksize) on the device
+_RS_TABLES_MAX = 32
+_RS_LOCK = threading.Lock()      # (the SAM2 prefetch thread resizes too)
+
+
+def _resample_tables(n_in: int, n_out: int, filter: str, device: torch.device):
+    """The taps of one axis on the device, built by hostops.pil_resample_coeffs and uploaded once per (in, out, filter, device); a small LRU."""
+    key = (int(n_in), int(n_out), filter, str(device))
+    with _RS_LOCK:
+        hit = _RS_TABLES.get(key)
+        if hit is not None:
+            _RS_TABLES.move_to_end(key)
+            return hit
+    kk, bounds = hostops.pil_resample_coeffs(n_in, n_out, filter)
+    hit = (torch.from_numpy(kk).to(device), torch.from_numpy(bounds).to(device), int(kk.shape[1]))
+    torch.cuda.current_stream(device).synchronize()      # once per table: later calls may use it from any stream
+    with _RS_LOCK:
+        _RS_TABLES[key] = hit
+        while len(_RS_TABLES) > _RS_TABLES_MAX:
+            _RS_TABLES.popitem(last=False)
+    return hit
+
+
+def resize_pil(src: torch.Tensor, H: int, W: int, filter: str = "bicubic") -> torch.Tensor:
+    """``Image.fromarray(src).resize((W, H), resample=filter)`` on the device, bit for bit (sr_resize_pil_u8): uint8 CUDA [h, w], [h, w, 3] or
+    [n, h, w, 3] -> the same rank, on the current stream of ``src.device``.  filter: "bicubic" | "bilinear" | "lanczos".  4 channels are refused
+    (PIL resizes RGBA through a premultiplied copy)."""
+    if filter not in hostops.PIL_FILTERS:
+        raise ValueError(f"filter {filter!r}: one of {sorted(hostops.PIL_FILTERS)}")
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
+        raise ValueError(f"src: dtype {getattr(src, 'dtype', type(src).__name__)}, a uint8 tensor expected")
+    if src.dim() == 4 and src.shape[3] == 3:
+        n, (h, w), ch = int(src.shape[0]), src.shape[1:3], 3
+    elif src.dim() == 3 and src.shape[2] == 3:
+        n, (h, w), ch = 1, src.shape[:2], 3
+    elif src.dim() == 2:
+        n, (h, w), ch = 1, src.shape, 1
+    else:
+        raise ValueError(f"src: shape {tuple(src.shape)}, [h, w], [h, w, 3] or [n, h, w, 3] expected"
+                         + (" (4 channels: PIL resizes RGBA through a premultiplied copy, which stays on the host)" if src.dim() >= 3 and src.shape[-1] == 4 else ""))
+    h, w, H, W = int(h), int(w), int(H), int(W)
+    if not (1 <= H <= 8192 and 1 <= W <= 8192 and 1 <= h <= 8192 and 1 <= w <= 8192) or n < 1:
+        raise ValueError(f"src / H / W: {n} image(s) of {h} x {w} -> {H} x {W}: every side must be in 1 .. 8192 and n >= 1")
+    if not src.is_cuda:
+        raise ValueError(f"src: a CUDA tensor expected, got device {src.device}")
+    src = src.contiguous()
+    dev = src.device
+    kh = _resample_tables(w, W, filter, dev) if w != W else (None, None, 0)
+    kv = _resample_tables(h, H, filter, dev) if h != H else (None, None, 0)
+    dst = torch.empty((n, H, W, ch), dtype=torch.uint8, device=dev)
+    tmp = torch.empty(n * h * W * ch, dtype=torch.uint8, device=dev) if (w != W and h != H) else None
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    L.check(L.load().sr_resize_pil_u8(p(src), h, w, p(dst), H, W, ch, n, p(kh[0]), p(kh[1]), kh[2], p(kv[0]), p(kv[1]), kv[2], p(tmp), _s(src)),
+            None, "sr_resize_pil_u8")
+    return dst.reshape((H, W) if src.dim() == 2 else (H, W, 3) if src.dim() == 3 else (n, H, W, 3))
 
 
 def iou_counts(pred: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:

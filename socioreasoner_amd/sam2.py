@@ -841,16 +841,22 @@ class Sam2Predictor:
     def predict(self, point_coords=None, point_labels=None, box=None, **kw):
         return self.engine.predict(point_coords, point_labels, box, **kw)
 
-    def embed(self, images: Sequence) -> List[dict]:
+    def embed(self, images: Sequence, resize_to: Optional[Tuple[int, int]] = None) -> List[dict]:
         """image embeddings of a list of host images: the ones seen before come from the cache (keyed by a hash of the pixels), the rest go
-        through the encoder ``batch`` at a time.  Same numbers either way: the encoder is deterministic and images do not interact."""
+        through the encoder ``batch`` at a time.  Same numbers either way: the encoder is deterministic and images do not interact.
+        resize_to=(h, w): the images are uploaded at their own size and brought to h x w on the upload stream by PIL's bicubic resize as a kernel
+        (raster.resize_pil: the pixels of ``image.resize((w, h))``, bit for bit); the cache key is then the hash of the SOURCE pixels plus the
+        source shape and the target size."""
         import xxhash
         with self._lock:
-            return self._embed_locked(images, xxhash)
+            return self._embed_locked(images, xxhash, resize_to)
 
-    def _embed_locked(self, images, xxhash):
+    def _embed_locked(self, images, xxhash, resize_to=None):
         arrs = [self._host_u8(im) for im in images]
         keys = [xxhash.xxh3_128_digest(a.data) + bytes(str(a.shape), "ascii") for a in arrs]
+        if resize_to is not None:
+            rh, rw = int(resize_to[0]), int(resize_to[1])
+            keys = [k + bytes(f"->{rh}x{rw}", "ascii") for k in keys]
         feats: Dict[bytes, dict] = {}
         todo = []
         for k, a in zip(keys, arrs):
@@ -872,6 +878,9 @@ class Sam2Predictor:
             # the previous chunk's encoder pass and the GPU would idle during the next uploads; on their own stream they overlap it
             with torch.cuda.stream(self._upload):
                 dev_imgs = [torch.from_numpy(by_key[k]).to(self.engine.device, non_blocking=True) for k in chunk]
+                if resize_to is not None:
+                    from . import raster
+                    dev_imgs = [t if tuple(t.shape[:2]) == (rh, rw) else raster.resize_pil(t, rh, rw, "bicubic") for t in dev_imgs]
                 up = torch.cuda.Event()
                 up.record(self._upload)
             main.wait_event(up)
@@ -890,12 +899,12 @@ class Sam2Predictor:
         self.stats["images"] += len(arrs)
         return [feats[k] for k in keys]
 
-    def prefetch(self, images: Sequence, prepare=None, chunk: Optional[int] = None) -> None:
+    def prefetch(self, images: Sequence, prepare=None, chunk: Optional[int] = None, resize_to: Optional[Tuple[int, int]] = None) -> None:
         """Start encoding `images` (host images, as `segment_batch` will receive them) on a background thread and a stream of its own; returns at once.
         `set_images` needs nothing but the pixels (seg_strategy.py:47-58), so the pipeline calls this before stage-1 generation: the encoder runs under
         the LM's generate call and `segment_batch` finds the embeddings in the cache (its own `embed` encodes whatever is still missing).  One chunk of
         `batch` images per lock hold, the side stream drained before the lock is released.  `prepare(image)` -- the caller's host-side preparation of one
-        image, e.g. seg_infer's 756 x 756 resize -- runs on the thread too, chunk by chunk."""
+        image, e.g. seg_infer's 756 x 756 resize -- runs on the thread too, chunk by chunk.  `resize_to`: as in `embed`."""
         import threading
         self.wait_prefetch()
         images = list(images)
@@ -915,7 +924,7 @@ class Sam2Predictor:
                         time.sleep(0.0005)           # first, which would be this loop again -- the foreground goes first
                     part = images[i:i + step] if prepare is None else [prepare(im) for im in images[i:i + step]]      # (host preparation outside the lock)
                     with self._lock, torch.cuda.stream(self._pf_stream):
-                        self.embed(part)
+                        self.embed(part, resize_to=resize_to)
                         self._pf_stream.synchronize()
             except Exception as e:  # noqa: BLE001  (reported by wait_prefetch / the next segment_batch; the embeddings it missed are encoded there)
                 self._pf_error = e
@@ -932,17 +941,18 @@ class Sam2Predictor:
             e, self._pf_error = self._pf_error, None
             raise RuntimeError("SAM2 prefetch failed") from e
 
-    def segment_batch(self, images: Sequence, prompts: Sequence[Sequence[dict]]) -> List[torch.Tensor]:
+    def segment_batch(self, images: Sequence, prompts: Sequence[Sequence[dict]], resize_to: Optional[Tuple[int, int]] = None) -> List[torch.Tensor]:
         """seg_strategy.py:40-66 over a whole batch: embeddings (batched / cached), then the object loop of every sample on the device.
         A prefetch that is still running is not waited for (the streamed two-stage pipeline segments its first samples while later ones are still being
-        encoded): this call goes ahead of the prefetch loop's next chunk, encodes what it misses itself, and the loop finds those in the cache."""
+        encoded): this call goes ahead of the prefetch loop's next chunk, encodes what it misses itself, and the loop finds those in the cache.
+        `resize_to`: as in `embed` (the masks are then resize_to's size)."""
         if self._pf_error is not None:
             self.wait_prefetch()
         out = []
         self._want += 1
         try:
             with self._lock:
-                for ft, vps in zip(self.embed(images), prompts):
+                for ft, vps in zip(self.embed(images, resize_to=resize_to), prompts):
                     self.engine.use_features(ft)
                     out.append(self.segment_objects(vps))
                 if self._pf_thread is not None:      # the prefetch loop may take the engine next, on another stream: leave this one drained (as it does)
