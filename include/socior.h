@@ -323,15 +323,40 @@ int sr_render_overlay(uint8_t* dev_img_rgb, int h, int w, const uint8_t* dev_mas
  *                         P = 0, not masked); items cut at q_tile queries.  It is used when n_heads % 4 == 0 and (head_dim 128, causal,
  *                         q_tile 64, group % 4 == 0) or (head_dim 80, not causal, q_tile 128, group 1), with bit-identical results;
  *                         q_tile 128 without it is refused.
- *   sr_op_sam_preprocess : uint8 HWC -> bf16 CHW [3][S][S], /255, bilinear resize, ImageNet normalisation.
- *   sr_op_im2col    : k x k / stride / pad windows of a CHW image -> GEMM operand rows (optional destination row map).
- *   sr_op_layernorm : LayerNorm with bias over C channels, pad columns [C, ldo) zeroed.
- *   sr_op_maxpool_win : 2 x 2 max pooling of tokens stored window by window.
- *   sr_op_ew        : mode 0 a + b, 1 a + row vector, 2 relu, 3 gelu (erf).
- *   sr_op_transpose : out[c][r] = in[r][c].
- *   sr_op_upsample2x_add : FPN top-down step.   sr_op_pixel_shuffle_add : second half of a 2 x 2 / stride 2 transposed convolution.
- *   sr_op_mask_resize_or : best (arg-max score) of n low-resolution logit maps, bilinear to h x w, > 0, OR into the object union.
- *   sr_op_gather_rows : out[i] = in[rows[i]]. */
+ *   The passes below work on row-major matrices [rows][ld] with C live columns (bf16 here, float32 in the _f32 forms further down).
+ *   Preconditions (the kernels check none of them unless a refusal is named; tests/sam2_ops_ref.py check_preconditions is their
+ *   executable form): every matrix holds (rows - 1) * ld + C elements from its pointer, ld >= C; elements are naturally aligned; an op
+ *   writes the live columns of its output rows and nothing else unless pad columns are named; what lies in the pad columns [C, ld) and in
+ *   the rows past the end of an input is never read (it may be NaN or inf).  Outputs may not overlap inputs except where "in place" is
+ *   named.  Rounding: one rounding to the storage type per op, float32 arithmetic inside.
+ *   sr_op_sam_preprocess : uint8 HWC [h][w][3] -> CHW [3][S][S]: /255, bilinear resize (align_corners false, no antialiasing), ImageNet
+ *                     normalisation.  h, w, S >= 1; img holds h * w * 3 bytes, out 3 * S * S elements.
+ *   sr_op_im2col    : k x k / stride / pad windows of a CHW image [3][S][S] -> rows [(ty, tx)][c * k * k + ky * k + kx] of T * T tokens,
+ *                     T = (S + 2 pad - k) / stride + 1 >= 1 (floor); zero beyond the image and in the pad columns [3 k k, ld), which this
+ *                     op owns.  rowmap (NULL = identity): T * T DISTINCT destination rows in [0, T * T).  ld < 3 k k returns -22.
+ *   sr_op_layernorm : LayerNorm with bias over C channels of each of `rows` rows (two-pass float32 statistics); the pad columns [C, ldo)
+ *                     are written as zeros, so out holds rows * ldo elements.  1 <= C <= ldo, ldx >= C; w and b hold C elements.  C or ldo
+ *                     above 1152 returns -22; rows <= 0 returns 0.  In place (out == x, ldo == ldx) is allowed.  bf16: 16-byte accesses
+ *                     when C, ldx and ldo are multiples of 8 and x, w, b, out 16-byte aligned, one channel per lane otherwise -- the same
+ *                     formula and rounding point, the statistics summed in another order.
+ *   sr_op_maxpool_win : 2 x 2 max pooling of tokens stored window by window: [n_win][ws * ws] rows -> [n_win][(ws / 2)^2] rows, C columns.
+ *                     n_win >= 1, ws >= 2; an odd ws returns -22.
+ *   sr_op_ew        : mode 0 a + b, 1 a + row vector b[0 .. C), 2 relu(a), 3 gelu(a) (erf form), 4 silu(a) * b; rows x C elements with
+ *                     leading dimensions lda / ldb / ldo.  b is not read in modes 2 / 3.  In place on a (out == a, ldo == lda) is allowed.
+ *                     rows <= 0 returns 0.
+ *   sr_op_transpose : out[c][r] = in[r][c] for rows x cols (bf16 only); writes columns [0, rows) of `cols` output rows, ld_out >= rows.
+ *                     16-byte accesses when cols, ld_in, ld_out are multiples of 8 and both pointers 16-byte aligned (any rows), element by
+ *                     element otherwise; the same bits either way.
+ *   sr_op_upsample2x_add : FPN top-down step out[y][x] = lat[y][x] + top[y / 2][x / 2] on an H2 x H2 grid of rows (top: H2 / 2 x H2 / 2),
+ *                     one ld for all three.  An odd H2 returns -22 (the top map has no row for y / 2 of the last row).
+ *   sr_op_pixel_shuffle_add : second half of a 2 x 2 / stride 2 transposed convolution: the GEMM wrote g [W * W][co * 4 + dy * 2 + dx]
+ *                     (ldg >= 4 Co); out[(2y + dy) * 2W + 2x + dx][co] = g[y * W + x][co * 4 + dy * 2 + dx] + feat[same row][co], 4 W W rows.
+ *   sr_op_mask_resize_or : low float32 [m * m][ld], column col0 + i = logit map i of n >= 1 (col0 + n <= ld); best = the FIRST arg-max of
+ *                     score[col0 .. col0 + n) (finite); that map, bilinear (align_corners false) to h x w, sets acc[i] = 1 where > 0 and
+ *                     leaves acc alone elsewhere (acc: h * w bytes, the running union).  logits_out (NULL or float32 [n][h * w]) receives all
+ *                     n resized maps and does not change acc.
+ *   sr_op_gather_rows : out[i] = in[rows[i]] for n rows of H bf16 elements (a float32 row of H / 2 floats is gathered with the doubled H);
+ *                     16 bytes per lane: in and out 16-byte aligned, rows[i] in range; H % 8 != 0 returns -22, n <= 0 returns 0. */
 int sr_op_attention(const void* q, int q_stride, const void* k, int k_stride, long long k_head_stride, const void* vt, int vt_stride,
                     long long vt_head_stride, void* out, int out_stride, const void* dev_work, int n_work, int n_heads, int group, float scale,
                     int causal, int head_dim, int q_tile, int v2_ok, void* stream);
@@ -349,7 +374,8 @@ int sr_op_gemm(const void* A, int lda, const void* W, int M, int N, int K, void*
                const void* resid, const int32_t* rowmap, int epilogue, void* stream);
 /* ---- SAM2 at the REFERENCE's precision.  The reference builds SAM2ImagePredictor(build_sam2(...)) in float32 and calls it without
  * autocast (/root/reference/roll/models/model_providers.py:540-548, roll/distributed/strategy/seg_strategy.py:47-60): these are the
- * float32 forms of the entry points above (same argument meaning, float32 row-major matrices [rows][ld], ld % 4 == 0, 16-byte aligned)
+ * float32 forms of the entry points above (same argument meaning, preconditions and refusals, float32 row-major matrices [rows][ld]; the
+ * GEMM and the attention need ld % 4 == 0 and 16-byte aligned pointers, the passes access element by element and take any ld >= C)
  * that socioreasoner_amd/sam2.py drives when Sam2Engine(dtype=float32) -- the default behind seg_infer.
  *   sr_op_gemm_f32      : out = act(A . W^T + bias) (+ resid), float32 in and out; epilogue 0 store, 1 residual, 3 GELU (erf form; | 0x1000 =
  *                         ReLU), 4 = 0; K % 16 == 0, N % 4 == 0.  Round 5: computed on the bf16 matrix pipe from an exact three-term bf16 split of

@@ -641,6 +641,7 @@ int launch_embed(hipStream_t s, const int* src, const bf16_t* table, const bf16_
 }
 int launch_gather_rows(hipStream_t s, const bf16_t* in, const int* rows, bf16_t* out, int n, int H) {
     if (n <= 0) return 0;
+    if (H % 8) return -22;                                  // 16 bytes per lane: the last H % 8 columns would be dropped
     hipLaunchKernelGGL(k_gather_rows, dim3(n), dim3(256), 0, s, in, rows, out, H);
     SR_CHECK_LAUNCH();
     return 0;

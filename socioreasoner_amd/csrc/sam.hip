@@ -307,6 +307,7 @@ int launch_ew_f32(hipStream_t s, const float* a, int lda, const float* b, int ld
     LAUNCH_OK();
 }
 int launch_upsample2x_add_f32(hipStream_t s, const float* lat, const float* top, float* out, int H2, int C, int ld) {
+    if (H2 % 2) return -22;                                 // row H2 / 2 of a top map of H2 / 2 rows (y / 2 of the last row) does not exist
     hipLaunchKernelGGL(k_upsample2x_add<float>, dim3((unsigned)(((long long)H2 * H2 * C + 255) / 256)), dim3(256), 0, s, lat, top, out, H2, C, ld);
     LAUNCH_OK();
 }
@@ -348,6 +349,7 @@ int launch_transpose(hipStream_t s, const bf16_t* in, int ld_in, int rows, int c
     LAUNCH_OK();
 }
 int launch_upsample2x_add(hipStream_t s, const bf16_t* lat, const bf16_t* top, bf16_t* out, int H2, int C, int ld) {
+    if (H2 % 2) return -22;
     hipLaunchKernelGGL(k_upsample2x_add<bf16_t>, dim3((unsigned)(((long long)H2 * H2 * C + 255) / 256)), dim3(256), 0, s, lat, top, out, H2, C, ld);
     LAUNCH_OK();
 }
