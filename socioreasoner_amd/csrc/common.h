@@ -25,6 +25,14 @@ __device__ __forceinline__ void rbf2(float& a, float& b) {
 }
 __device__ __forceinline__ float lo16(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float hi16(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+// 16 bytes = 8 bf16 <-> 8 floats, element e in the low (even e) / high (odd e) half of dword e / 2
+__device__ __forceinline__ void unpack8(uint4 u, float (&f)[8]) {
+    f[0] = lo16(u.x); f[1] = hi16(u.x); f[2] = lo16(u.y); f[3] = hi16(u.y);
+    f[4] = lo16(u.z); f[5] = hi16(u.z); f[6] = lo16(u.w); f[7] = hi16(u.w);
+}
+__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+    return uint4{pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7])};
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -35,6 +43,30 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// ---- RMSNorm over 8-channel chunks (hf:65-79), each step stated once for k_rmsnorm / k_rmsnorm_mx (elementwise.hip) and rmsnorm_row_body (rownorm.h)
+__device__ __forceinline__ void rms_slab_acc(float (&a)[8], float4 p0, float4 p1) {      // a += one pending float32 slab
+    a[0] += p0.x; a[1] += p0.y; a[2] += p0.z; a[3] += p0.w;
+    a[4] += p1.x; a[5] += p1.y; a[6] += p1.z; a[7] += p1.w;
+}
+// the fused residual: v = bf16(v + bf16(sum of slabs)), written back to the residual stream
+__device__ __forceinline__ void rms_resid(float (&v)[8], const float (&a)[8], bf16_t* x) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = rbf(v[e] + rbf(a[e]));
+    *reinterpret_cast<uint4*>(x) = pack8(v);
+}
+__device__ __forceinline__ float rms_sumsq(const float (&v)[8], float ss) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ss += v[e] * v[e];
+    return ss;
+}
+__device__ __forceinline__ float rms_rs(float ss, int H, float eps) { return 1.0f / sqrtf(ss / (float)H + eps); }
+__device__ __forceinline__ void rms_scale(const float (&v)[8], uint4 wu, float rs, float (&o)[8]) {      // o = w * bf16(v * rs), not yet rounded
+    float wv[8];
+    unpack8(wu, wv);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = wv[e] * rbf(v[e] * rs);
 }
 
 // Block bid of an nblk-block 1-D grid runs on XCD bid % 8.  Returns the work unit it should take so that every XCD works on ONE

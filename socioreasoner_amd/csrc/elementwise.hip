@@ -5,56 +5,54 @@
 #include "kernels.h"
 #include "rownorm.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
 // ----------------------------------------------------------------------------------------------- RMSNorm (hf:65-79)
 // One wave per row.  Optional fused residual: h = bf16(x + bf16(sum_ks part[ks])) is written back to x first.
+// The wave's pass over its row, shared with k_rmsnorm_mx: lane holds the 8-channel chunks lane + 64 i in v; returns 1 / rms of the row.
+// (a lane's chunks are an array of structs, not float[MAXC][8]: the helpers reach the kernels with their 8-element loops already unrolled, and the
+// compiler then turns a plain 2-D array into ONE 32-wide vector before the chunk loop is unrolled -- k_rmsnorm_mx<4> 60 -> 84 registers, 8 -> 5 waves)
+struct chunk8 { float f[8]; };
+template <int MAXC>
+__device__ __forceinline__ float rms_wave_load(bf16_t* x, const bf16_t* xin, const float* part, int ksplit, int rows, int row, int H, float eps,
+                                               chunk8 (&v)[MAXC]) {
+    const int lane = threadIdx.x & 63, nch = H / 8;
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+        const int c = lane + i * 64;
+        if (c < nch) {
+            unpack8(*reinterpret_cast<const uint4*>(xin + (size_t)row * H + c * 8), v[i].f);
+            if (part) {
+                float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                for (int ks = 0; ks < ksplit; ++ks) {
+                    const float4* pp = reinterpret_cast<const float4*>(part + ((size_t)ks * rows + row) * H + c * 8);
+                    rms_slab_acc(a, pp[0], pp[1]);
+                }
+                rms_resid(v[i].f, a, x + (size_t)row * H + c * 8);
+            }
+            ss = rms_sumsq(v[i].f, ss);
+        }
+    }
+    return rms_rs(wave_sum(ss), H, eps);
+}
 template <int MAXC>
 __global__ __launch_bounds__(256) void k_rmsnorm(bf16_t* x, const bf16_t* xin, const float* part, int ksplit,
                                                  const bf16_t* w, bf16_t* out, int rows, int H, float eps) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     const int nch = H / 8;
-    float v[MAXC][8];
-    float ss = 0.f;
+    chunk8 v[MAXC];
+    const float rs = rms_wave_load<MAXC>(x, xin, part, ksplit, rows, row, H, eps, v);
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
         const int c = lane + i * 64;
         if (c < nch) {
-            uint4 u = *reinterpret_cast<const uint4*>(xin + (size_t)row * H + c * 8);
-            v[i][0] = lo16(u.x); v[i][1] = hi16(u.x); v[i][2] = lo16(u.y); v[i][3] = hi16(u.y);
-            v[i][4] = lo16(u.z); v[i][5] = hi16(u.z); v[i][6] = lo16(u.w); v[i][7] = hi16(u.w);
-            if (part) {
-                float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                for (int ks = 0; ks < ksplit; ++ks) {
-                    const float4* pp = reinterpret_cast<const float4*>(part + ((size_t)ks * rows + row) * H + c * 8);
-                    float4 p0 = pp[0], p1 = pp[1];
-                    a[0] += p0.x; a[1] += p0.y; a[2] += p0.z; a[3] += p0.w;
-                    a[4] += p1.x; a[5] += p1.y; a[6] += p1.z; a[7] += p1.w;
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[i][e] = rbf(v[i][e] + rbf(a[e]));
-                uint4 o = {pack2(v[i][0], v[i][1]), pack2(v[i][2], v[i][3]), pack2(v[i][4], v[i][5]), pack2(v[i][6], v[i][7])};
-                *reinterpret_cast<uint4*>(x + (size_t)row * H + c * 8) = o;
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ss += v[i][e] * v[i][e];
-        }
-    }
-    ss = wave_sum(ss);
-    const float rs = 1.0f / sqrtf(ss / (float)H + eps);
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-        const int c = lane + i * 64;
-        if (c < nch) {
-            uint4 wu = *reinterpret_cast<const uint4*>(w + c * 8);
-            float wv[8] = {lo16(wu.x), hi16(wu.x), lo16(wu.y), hi16(wu.y), lo16(wu.z), hi16(wu.z), lo16(wu.w), hi16(wu.w)};
             float o[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = wv[e] * rbf(v[i][e] * rs);
-            uint4 ov = {pack2(o[0], o[1]), pack2(o[2], o[3]), pack2(o[4], o[5]), pack2(o[6], o[7])};
-            *reinterpret_cast<uint4*>(out + (size_t)row * H + c * 8) = ov;
+            rms_scale(v[i].f, *reinterpret_cast<const uint4*>(w + c * 8), rs, o);
+            *reinterpret_cast<uint4*>(out + (size_t)row * H + c * 8) = pack8(o);
         }
     }
 }
@@ -84,8 +82,9 @@ __global__ __launch_bounds__(256) void k_vit_rope(bf16_t* qkv, int n_rows, int n
     const float4* cp = reinterpret_cast<const float4*>(cos_t + (size_t)row * half + c * 8);
     const float4* sp = reinterpret_cast<const float4*>(sin_t + (size_t)row * half + c * 8);
     const float4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
-    const float x1[8] = {lo16(u1.x), hi16(u1.x), lo16(u1.y), hi16(u1.y), lo16(u1.z), hi16(u1.z), lo16(u1.w), hi16(u1.w)};
-    const float x2[8] = {lo16(u2.x), hi16(u2.x), lo16(u2.y), hi16(u2.y), lo16(u2.z), hi16(u2.z), lo16(u2.w), hi16(u2.w)};
+    float x1[8], x2[8];
+    unpack8(u1, x1);
+    unpack8(u2, x2);
     const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, ss[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
     float o1[8], o2[8];
 #pragma unroll
@@ -93,8 +92,8 @@ __global__ __launch_bounds__(256) void k_vit_rope(bf16_t* qkv, int n_rows, int n
         o1[e] = __fadd_rn(__fmul_rn(x1[e], cc[e]), __fmul_rn(-x2[e], ss[e]));
         o2[e] = __fadd_rn(__fmul_rn(x2[e], cc[e]), __fmul_rn(x1[e], ss[e]));
     }
-    *reinterpret_cast<uint4*>(p) = uint4{pack2(o1[0], o1[1]), pack2(o1[2], o1[3]), pack2(o1[4], o1[5]), pack2(o1[6], o1[7])};
-    *reinterpret_cast<uint4*>(p2) = uint4{pack2(o2[0], o2[1]), pack2(o2[2], o2[3]), pack2(o2[4], o2[5]), pack2(o2[6], o2[7])};
+    *reinterpret_cast<uint4*>(p) = pack8(o1);
+    *reinterpret_cast<uint4*>(p2) = pack8(o2);
 }
 
 // V^T for the attention kernel: vt[h][d][row] = qkv[row][2C + h*hd + d]; 64 rows x one head per block via LDS, 16-byte
@@ -379,7 +378,32 @@ __global__ void k_rows_abort(uint4 mask, int* finished) {
     if (threadIdx.x < 128 && ((word >> (threadIdx.x & 31)) & 1u)) finished[threadIdx.x] = 1;
 }
 
-// fp8 weight quantisation, one block per 16-row tile of a fragment-ordered bf16 matrix (see kernels.h)
+// fp8 weight quantisation (scale[n] = amax_n / 448, 1 for a zero row; q = fp8(W / scale)), one block per 16-row tile, 16 threads per row.
+// The steps k_quant_f8 and k_quant_f8_rows share:
+__device__ __forceinline__ float absmax8(const float (&f)[8], float mx) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(f[e]));
+    return mx;
+}
+// the LDS reduction: thread `slot` of row `row` publishes its maximum; thread r < 16 returns row r's (the others 0)
+__device__ __forceinline__ float row_amax16(float (&amax_s)[16][17], int row, int slot, float mx) {
+    amax_s[row][slot] = mx;
+    __syncthreads();
+    float m = 0.f;
+    if (threadIdx.x < 16)
+        for (int j = 0; j < 16; ++j) m = fmaxf(m, amax_s[threadIdx.x][j]);
+    return m;
+}
+__device__ __forceinline__ float f8_row_scale(float m) { return m > 0.f ? __fdiv_rn(m, 448.0f) : 1.0f; }
+__device__ __forceinline__ void cvt8_f8(const float (&f)[8], float sc, int& p0, int& p1) {
+    p0 = 0, p1 = 0;
+    p0 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[0], sc), __fdiv_rn(f[1], sc), p0, false);
+    p0 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[2], sc), __fdiv_rn(f[3], sc), p0, true);
+    p1 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[4], sc), __fdiv_rn(f[5], sc), p1, false);
+    p1 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[6], sc), __fdiv_rn(f[7], sc), p1, true);
+}
+
+// a fragment-ordered bf16 matrix (see kernels.h): fp8 image + the bf16 master replaced by its dequantised value
 __global__ __launch_bounds__(256) void k_quant_f8(bf16_t* W, int K, unsigned char* W8, float* scale) {
     __shared__ float amax_s[16][17];
     __shared__ float sc_s[16];
@@ -388,35 +412,22 @@ __global__ __launch_bounds__(256) void k_quant_f8(bf16_t* W, int K, unsigned cha
     // vector v of the tile: chunk = v >> 7, kstep = (v >> 6) & 1, lane = v & 63, row = lane & 15 = v & 15.  A thread's
     // vectors (v = tid + 256 j) all belong to row tid & 15.
     const int nvec = 16 * K / 8;                              // 16-byte vectors
-    float mx = 0.f;
+    float mx = 0.f, f[8];
     for (int v = tid; v < nvec; v += 256) {
-        const uint4 u = *reinterpret_cast<const uint4*>(wt + (size_t)v * 8);
-        const float f[8] = {lo16(u.x), hi16(u.x), lo16(u.y), hi16(u.y), lo16(u.z), hi16(u.z), lo16(u.w), hi16(u.w)};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(f[e]));
+        unpack8(*reinterpret_cast<const uint4*>(wt + (size_t)v * 8), f);
+        mx = absmax8(f, mx);
     }
     // thread tid owns row tid & 15; 16 threads per row
-    amax_s[tid & 15][tid >> 4] = mx;
-    __syncthreads();
-    if (tid < 16) {
-        float m = 0.f;
-        for (int j = 0; j < 16; ++j) m = fmaxf(m, amax_s[tid][j]);
-        const float sc = m > 0.f ? __fdiv_rn(m, 448.0f) : 1.0f;
-        sc_s[tid] = sc;
-        scale[tile * 16 + tid] = sc;
-    }
+    const float m = row_amax16(amax_s, tid & 15, tid >> 4, mx);
+    if (tid < 16) scale[tile * 16 + tid] = sc_s[tid] = f8_row_scale(m);
     __syncthreads();
     const float sc = sc_s[tid & 15];
     unsigned char* w8t = W8 + (size_t)tile * 16 * K;          // tiled8: the tile's 16 x K bytes are contiguous
     for (int v = tid; v < nvec; v += 256) {
         const int chunk = v >> 7, kstep = (v >> 6) & 1, lane = v & 63;
-        uint4 u = *reinterpret_cast<const uint4*>(wt + (size_t)v * 8);
-        const float f[8] = {lo16(u.x), hi16(u.x), lo16(u.y), hi16(u.y), lo16(u.z), hi16(u.z), lo16(u.w), hi16(u.w)};
-        int p0 = 0, p1 = 0;
-        p0 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[0], sc), __fdiv_rn(f[1], sc), p0, false);
-        p0 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[2], sc), __fdiv_rn(f[3], sc), p0, true);
-        p1 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[4], sc), __fdiv_rn(f[5], sc), p1, false);
-        p1 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[6], sc), __fdiv_rn(f[7], sc), p1, true);
+        unpack8(*reinterpret_cast<const uint4*>(wt + (size_t)v * 8), f);
+        int p0, p1;
+        cvt8_f8(f, sc, p0, p1);
         *reinterpret_cast<uint2*>(w8t + ((size_t)chunk * 64 + lane) * 16 + kstep * 8) = uint2{(uint32_t)p0, (uint32_t)p1};
         uint32_t a0, a1, b0, b1;
         f8x4_to_bf16((uint32_t)p0, a0, a1);
@@ -454,27 +465,28 @@ __global__ __launch_bounds__(256) void k_quant_mx_act(const bf16_t* x, int ldx, 
     const int m = (int)(t / nb), b = (int)(t % nb);
     const uint4* src = reinterpret_cast<const uint4*>(x + (size_t)m * ldx + b * 32);
     uint4 u[4] = {src[0], src[1], src[2], src[3]};
-    float v[32];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[i * 8 + 0] = lo16(u[i].x); v[i * 8 + 1] = hi16(u[i].x); v[i * 8 + 2] = lo16(u[i].y); v[i * 8 + 3] = hi16(u[i].y);
-        v[i * 8 + 4] = lo16(u[i].z); v[i * 8 + 5] = hi16(u[i].z); v[i * 8 + 6] = lo16(u[i].w); v[i * 8 + 7] = hi16(u[i].w);
-    }
+    float v[4][8];
     float amax = 0.f;
 #pragma unroll
-    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
+    for (int i = 0; i < 4; ++i) {
+        unpack8(u[i], v[i]);
+        amax = absmax8(v[i], amax);
+    }
     const int e = mx_block_exp(amax);
     const float inv2 = mx_inv_scale(e);
     int p[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) p[i] = mx_cvt4(v[4 * i + 0], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], inv2);
+    for (int i = 0; i < 4; ++i) {
+        p[2 * i] = mx_cvt4(v[i][0], v[i][1], v[i][2], v[i][3], inv2);
+        p[2 * i + 1] = mx_cvt4(v[i][4], v[i][5], v[i][6], v[i][7], inv2);
+    }
     uint4* dst = reinterpret_cast<uint4*>(q + (size_t)m * K + b * 32);
     dst[0] = uint4{(uint32_t)p[0], (uint32_t)p[1], (uint32_t)p[2], (uint32_t)p[3]};
     dst[1] = uint4{(uint32_t)p[4], (uint32_t)p[5], (uint32_t)p[6], (uint32_t)p[7]};
     scales[((size_t)(b >> 2) * rows_pad + m) * 4 + (b & 3)] = (unsigned char)(e + 127);
 }
 
-// The vision tower's RMSNorm (k_rmsnorm, one wave per row: same loads, same order of the float32 sums, same two roundings) with the MX
+// The vision tower's RMSNorm (k_rmsnorm, one wave per row: its rms_wave_load and rms_scale, so the same loads, float32 sums and two roundings) with the MX
 // quantiser fused: the normalised bf16 row stays in registers and leaves as fp8 bytes + e8m0 block scales -- the bytes launch_rmsnorm
 // (per_wave) followed by k_quant_mx_act write, without the bf16 round trip through HBM (v_weight_dtype 2: nothing else reads v_xn).
 // A lane's 8 channels are a quarter of a 32-wide block: lanes 4j .. 4j + 3 of one pass share the block, its maximum is two lane exchanges.
@@ -487,35 +499,19 @@ __global__ __launch_bounds__(256) void k_rmsnorm_mx(const bf16_t* xin, const bf1
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     const int nch = H / 8;
-    float v[MAXC][8];
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-        const int c = lane + i * 64;
-        if (c < nch) {
-            uint4 u = *reinterpret_cast<const uint4*>(xin + (size_t)row * H + c * 8);
-            v[i][0] = lo16(u.x); v[i][1] = hi16(u.x); v[i][2] = lo16(u.y); v[i][3] = hi16(u.y);
-            v[i][4] = lo16(u.z); v[i][5] = hi16(u.z); v[i][6] = lo16(u.w); v[i][7] = hi16(u.w);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ss += v[i][e] * v[i][e];
-        }
-    }
-    ss = wave_sum(ss);
-    const float rs = 1.0f / sqrtf(ss / (float)H + eps);
+    chunk8 v[MAXC];
+    const float rs = rms_wave_load<MAXC>(nullptr, xin, nullptr, 0, rows, row, H, eps, v);          // k_rmsnorm's own pass, no pending slabs
     const int m = row / group, b0 = (row % group) * (H / 32);              // GEMM row, first 32-wide block of this normalised row inside it
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
         const int c = lane + i * 64;                                       // (H % 32 == 0: the four lanes of a block are in or out together)
         float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (c < nch) {
-            uint4 wu = *reinterpret_cast<const uint4*>(w + c * 8);
-            float wv[8] = {lo16(wu.x), hi16(wu.x), lo16(wu.y), hi16(wu.y), lo16(wu.z), hi16(wu.z), lo16(wu.w), hi16(wu.w)};
+            rms_scale(v[i].f, *reinterpret_cast<const uint4*>(w + c * 8), rs, o);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = rbf(wv[e] * rbf(v[i][e] * rs));      // the bf16 value k_rmsnorm stores
+            for (int e = 0; e < 8; ++e) o[e] = rbf(o[e]);                          // the bf16 value k_rmsnorm stores
         }
-        float amax = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(o[e]));
+        float amax = absmax8(o, 0.f);
         amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
         amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
         if (c < nch) {
@@ -529,40 +525,26 @@ __global__ __launch_bounds__(256) void k_rmsnorm_mx(const bf16_t* xin, const bf1
     }
 }
 
-// fp8 image of a ROW-MAJOR bf16 matrix [N][ld] (the vision tower keeps its weights row-major): same definition as k_quant_f8 (scale[n] =
-// amax_n / 448, 1 for a zero row; q = fp8(W / scale)), written as the tiled8 image the block-scaled GEMM stages.  The bf16 master is
-// left as it is, so a reload can quantise the matrix again.  One block per 16-row tile, 16 threads per row.
+// fp8 image of a ROW-MAJOR bf16 matrix [N][ld] (the vision tower keeps its weights row-major): k_quant_f8's steps, written as the tiled8
+// image the block-scaled GEMM stages.  The bf16 master is left as it is, so a reload can quantise the matrix again.
 __global__ __launch_bounds__(256) void k_quant_f8_rows(const bf16_t* W, int K, unsigned char* W8, float* scale) {
     __shared__ float amax_s[16][17];
     __shared__ float sc_s[16];
     const int tid = threadIdx.x, r = tid >> 4, t16 = tid & 15, n = blockIdx.x * 16 + r;
     const bf16_t* wr = W + (size_t)n * K;
-    float mx = 0.f;
+    float mx = 0.f, f[8];
     for (int k = t16 * 8; k < K; k += 128) {
-        const uint4 u = *reinterpret_cast<const uint4*>(wr + k);
-        const float f[8] = {lo16(u.x), hi16(u.x), lo16(u.y), hi16(u.y), lo16(u.z), hi16(u.z), lo16(u.w), hi16(u.w)};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(f[e]));
+        unpack8(*reinterpret_cast<const uint4*>(wr + k), f);
+        mx = absmax8(f, mx);
     }
-    amax_s[r][t16] = mx;
-    __syncthreads();
-    if (tid < 16) {
-        float m = 0.f;
-        for (int j = 0; j < 16; ++j) m = fmaxf(m, amax_s[tid][j]);
-        const float sc = m > 0.f ? __fdiv_rn(m, 448.0f) : 1.0f;
-        sc_s[tid] = sc;
-        scale[blockIdx.x * 16 + tid] = sc;
-    }
+    const float m = row_amax16(amax_s, r, t16, mx);
+    if (tid < 16) scale[blockIdx.x * 16 + tid] = sc_s[tid] = f8_row_scale(m);
     __syncthreads();
     const float sc = sc_s[r];
     for (int k = t16 * 8; k < K; k += 128) {
-        const uint4 u = *reinterpret_cast<const uint4*>(wr + k);
-        const float f[8] = {lo16(u.x), hi16(u.x), lo16(u.y), hi16(u.y), lo16(u.z), hi16(u.z), lo16(u.w), hi16(u.w)};
-        int p0 = 0, p1 = 0;
-        p0 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[0], sc), __fdiv_rn(f[1], sc), p0, false);
-        p0 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[2], sc), __fdiv_rn(f[3], sc), p0, true);
-        p1 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[4], sc), __fdiv_rn(f[5], sc), p1, false);
-        p1 = __builtin_amdgcn_cvt_pk_fp8_f32(__fdiv_rn(f[6], sc), __fdiv_rn(f[7], sc), p1, true);
+        unpack8(*reinterpret_cast<const uint4*>(wr + k), f);
+        int p0, p1;
+        cvt8_f8(f, sc, p0, p1);
         *reinterpret_cast<uint2*>(W8 + tiled8_offset((size_t)n, (size_t)k, (size_t)K)) = uint2{(uint32_t)p0, (uint32_t)p1};
     }
 }
@@ -579,28 +561,35 @@ int launch_load2d(hipStream_t s, const void* src, int dtype, long long rows, lon
     return 0;
 }
 
-int launch_rmsnorm(hipStream_t s, const bf16_t* x, const bf16_t* w, bf16_t* out, int rows, int H, float eps, int out_tiled, int per_wave) {
+// The wave-per-row RMSNorm kernels (k_rmsnorm, k_rmsnorm_mx): a lane holds MAXC chunks of 8 channels, 4 for rows up to 2048 wide, 12 up to RMS_MAX_H.
+// launch(mc) gets MAXC as decltype(mc)::value.
+constexpr int RMS_MAX_H = 64 * 8 * 12;
+template <typename F>
+static void rms_by_width(int H, F launch) {
+    if (H <= 2048) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, 12>{});
+}
+// x (+ pending slabs `part`, written back to x when there are any) -> out: the one body of launch_rmsnorm and launch_resid_rmsnorm
+static int rmsnorm_any(hipStream_t s, bf16_t* x, const bf16_t* xin, const float* part, int ksplit, const bf16_t* w, bf16_t* out, int rows, int H,
+                       int H_max, float eps, int out_tiled, int per_wave) {
     if (rows <= 0) return 0;
-    if (H % 8 != 0 || H > 64 * 8 * 12) return -22;
-    if (out_tiled && !(rows <= 128 && H <= 2048 && H % 64 == 0)) return -22;
-    dim3 g(cdiv(rows, 4)), b(256);
+    if (H % 8 != 0 || H > H_max) return -22;
+    const bool row_ok = rows <= 128 && H <= 2048 && ksplit <= 4;          // k_rmsnorm_row's shapes
+    if (out_tiled && !(row_ok && H % 64 == 0)) return -22;
     if (out_tiled && per_wave) return -22;
-    if (!per_wave && rows <= 128 && H <= 2048) hipLaunchKernelGGL(k_rmsnorm_row, dim3(rows), b, 0, s, (bf16_t*)nullptr, x, (const float*)nullptr, 0, w, out, rows, H, eps, out_tiled);
-    else if (H <= 2048) hipLaunchKernelGGL((k_rmsnorm<4>), g, b, 0, s, (bf16_t*)nullptr, x, (const float*)nullptr, 0, w, out, rows, H, eps);
-    else hipLaunchKernelGGL((k_rmsnorm<12>), g, b, 0, s, (bf16_t*)nullptr, x, (const float*)nullptr, 0, w, out, rows, H, eps);
+    if (!per_wave && row_ok) hipLaunchKernelGGL(k_rmsnorm_row, dim3(rows), dim3(256), 0, s, x, xin, part, ksplit, w, out, rows, H, eps, out_tiled);
+    else rms_by_width(H, [&](auto mc) {
+        hipLaunchKernelGGL((k_rmsnorm<decltype(mc)::value>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, xin, part, ksplit, w, out, rows, H, eps);
+    });
     SR_CHECK_LAUNCH();
     return 0;
 }
+int launch_rmsnorm(hipStream_t s, const bf16_t* x, const bf16_t* w, bf16_t* out, int rows, int H, float eps, int out_tiled, int per_wave) {
+    return rmsnorm_any(s, nullptr, x, nullptr, 0, w, out, rows, H, RMS_MAX_H, eps, out_tiled, per_wave);
+}
 int launch_resid_rmsnorm(hipStream_t s, bf16_t* x, const float* part, int ksplit, const bf16_t* w, bf16_t* out, int rows,
                          int H, float eps, int out_tiled, int per_wave) {
-    if (rows <= 0) return 0;
-    if (H % 8 != 0 || H > 2048) return -22;
-    if (out_tiled && !(rows <= 128 && ksplit <= 4 && H % 64 == 0)) return -22;
-    if (out_tiled && per_wave) return -22;
-    if (!per_wave && rows <= 128 && ksplit <= 4) hipLaunchKernelGGL(k_rmsnorm_row, dim3(rows), dim3(256), 0, s, x, (const bf16_t*)x, part, ksplit, w, out, rows, H, eps, out_tiled);
-    else hipLaunchKernelGGL((k_rmsnorm<4>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, (const bf16_t*)x, part, ksplit, w, out, rows, H, eps);
-    SR_CHECK_LAUNCH();
-    return 0;
+    return rmsnorm_any(s, x, x, part, ksplit, w, out, rows, H, 2048, eps, out_tiled, per_wave);
 }
 int launch_vit_rope(hipStream_t s, bf16_t* qkv, int n_rows, int n_heads, int head_dim, const float* cos_t,
                     const float* sin_t, bf16_t* vt, int vt_stride, int paired) {
@@ -710,10 +699,10 @@ int launch_quant_mx_act(hipStream_t s, const bf16_t* x, int ldx, int M, int K, u
 }
 int launch_rmsnorm_mx(hipStream_t s, const bf16_t* x, const bf16_t* w, unsigned char* q, unsigned char* scales, int rows, int H, float eps, int group, int rows_pad) {
     if (rows <= 0) return 0;
-    if (H % 128 != 0 || H > 64 * 8 * 12 || group < 1 || rows % group != 0 || rows_pad < rows / group) return -22;
-    dim3 g(cdiv(rows, 4)), b(256);
-    if (H <= 2048) hipLaunchKernelGGL((k_rmsnorm_mx<4>), g, b, 0, s, x, w, q, scales, rows, H, eps, group, rows_pad);      // (the same split as launch_rmsnorm)
-    else hipLaunchKernelGGL((k_rmsnorm_mx<12>), g, b, 0, s, x, w, q, scales, rows, H, eps, group, rows_pad);
+    if (H % 128 != 0 || H > RMS_MAX_H || group < 1 || rows % group != 0 || rows_pad < rows / group) return -22;
+    rms_by_width(H, [&](auto mc) {
+        hipLaunchKernelGGL((k_rmsnorm_mx<decltype(mc)::value>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, q, scales, rows, H, eps, group, rows_pad);
+    });
     SR_CHECK_LAUNCH();
     return 0;
 }

@@ -2054,28 +2054,28 @@ int sr_op_attention(const void* q, int q_stride, const void* k, int k_stride, lo
     SR_WRAP(launch_attn_prefill((hipStream_t)stream, a, head_dim));
 }
 int sr_op_sam_preprocess(const uint8_t* img, int h, int w, void* out_chw, int S, void* stream) {
-    SR_WRAP(launch_sam_preprocess((hipStream_t)stream, img, h, w, (bf16_t*)out_chw, S));
+    SR_WRAP(launch_sam_preprocess<bf16_t>((hipStream_t)stream, img, h, w, (bf16_t*)out_chw, S));
 }
 int sr_op_im2col(const void* chw, int S, int k, int stride, int pad, void* out, int ld, const int32_t* rowmap, void* stream) {
-    SR_WRAP(launch_im2col((hipStream_t)stream, (const bf16_t*)chw, S, k, stride, pad, (bf16_t*)out, ld, rowmap));
+    SR_WRAP(launch_im2col<bf16_t>((hipStream_t)stream, (const bf16_t*)chw, S, k, stride, pad, (bf16_t*)out, ld, rowmap));
 }
 int sr_op_layernorm(const void* x, int ldx, const void* w, const void* b, void* out, int ldo, int rows, int C, float eps, void* stream) {
-    SR_WRAP(launch_layernorm((hipStream_t)stream, (const bf16_t*)x, ldx, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)out, ldo, rows, C, eps));
+    SR_WRAP(launch_layernorm<bf16_t>((hipStream_t)stream, (const bf16_t*)x, ldx, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)out, ldo, rows, C, eps));
 }
 int sr_op_maxpool_win(const void* in, int ld_in, int C, int n_win, int ws, void* out, int ld_out, void* stream) {
-    SR_WRAP(launch_maxpool_win((hipStream_t)stream, (const bf16_t*)in, ld_in, C, n_win, ws, (bf16_t*)out, ld_out));
+    SR_WRAP(launch_maxpool_win<bf16_t>((hipStream_t)stream, (const bf16_t*)in, ld_in, C, n_win, ws, (bf16_t*)out, ld_out));
 }
 int sr_op_ew(const void* a, int lda, const void* b, int ldb, void* out, int ldo, int rows, int C, int mode, void* stream) {
-    SR_WRAP(launch_ew((hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb, (bf16_t*)out, ldo, rows, C, mode));
+    SR_WRAP(launch_ew<bf16_t>((hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb, (bf16_t*)out, ldo, rows, C, mode));
 }
 int sr_op_transpose(const void* in, int ld_in, int rows, int cols, void* out, int ld_out, void* stream) {
     SR_WRAP(launch_transpose((hipStream_t)stream, (const bf16_t*)in, ld_in, rows, cols, (bf16_t*)out, ld_out));
 }
 int sr_op_upsample2x_add(const void* lat, const void* top, void* out, int H2, int C, int ld, void* stream) {
-    SR_WRAP(launch_upsample2x_add((hipStream_t)stream, (const bf16_t*)lat, (const bf16_t*)top, (bf16_t*)out, H2, C, ld));
+    SR_WRAP(launch_upsample2x_add<bf16_t>((hipStream_t)stream, (const bf16_t*)lat, (const bf16_t*)top, (bf16_t*)out, H2, C, ld));
 }
 int sr_op_pixel_shuffle_add(const void* g, int ldg, const void* feat, int ldf, void* out, int ldo, int W, int Co, void* stream) {
-    SR_WRAP(launch_pixel_shuffle_add((hipStream_t)stream, (const bf16_t*)g, ldg, (const bf16_t*)feat, ldf, (bf16_t*)out, ldo, W, Co));
+    SR_WRAP(launch_pixel_shuffle_add<bf16_t>((hipStream_t)stream, (const bf16_t*)g, ldg, (const bf16_t*)feat, ldf, (bf16_t*)out, ldo, W, Co));
 }
 int sr_op_mask_resize_or(const float* low, int ld, int col0, int n, int m, const float* score, uint8_t* acc, float* logits_out, int h, int w, void* stream) {
     SR_WRAP(launch_mask_resize_or((hipStream_t)stream, low, ld, col0, n, m, score, acc, logits_out, h, w));
@@ -2112,25 +2112,25 @@ int sr_op_rope_table_f32(const float* inv_freq, int n_freq, const int32_t* pos, 
     SR_WRAP(launch_rope_table_f32((hipStream_t)stream, inv_freq, n_freq, pos, n_pos, cos_t, sin_t));
 }
 int sr_op_sam_preprocess_f32(const uint8_t* img, int h, int w, float* out_chw, int S, void* stream) {
-    SR_WRAP(launch_sam_preprocess_f32((hipStream_t)stream, img, h, w, out_chw, S));
+    SR_WRAP(launch_sam_preprocess<float>((hipStream_t)stream, img, h, w, out_chw, S));
 }
 int sr_op_im2col_f32(const float* chw, int S, int k, int stride, int pad, float* out, int ld, const int32_t* rowmap, void* stream) {
-    SR_WRAP(launch_im2col_f32((hipStream_t)stream, chw, S, k, stride, pad, out, ld, rowmap));
+    SR_WRAP(launch_im2col<float>((hipStream_t)stream, chw, S, k, stride, pad, out, ld, rowmap));
 }
 int sr_op_layernorm_f32(const float* x, int ldx, const float* w, const float* b, float* out, int ldo, int rows, int C, float eps, void* stream) {
-    SR_WRAP(launch_layernorm_f32((hipStream_t)stream, x, ldx, w, b, out, ldo, rows, C, eps));
+    SR_WRAP(launch_layernorm<float>((hipStream_t)stream, x, ldx, w, b, out, ldo, rows, C, eps));
 }
 int sr_op_maxpool_win_f32(const float* in, int ld_in, int C, int n_win, int ws, float* out, int ld_out, void* stream) {
-    SR_WRAP(launch_maxpool_win_f32((hipStream_t)stream, in, ld_in, C, n_win, ws, out, ld_out));
+    SR_WRAP(launch_maxpool_win<float>((hipStream_t)stream, in, ld_in, C, n_win, ws, out, ld_out));
 }
 int sr_op_ew_f32(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int rows, int C, int mode, void* stream) {
-    SR_WRAP(launch_ew_f32((hipStream_t)stream, a, lda, b, ldb, out, ldo, rows, C, mode));
+    SR_WRAP(launch_ew<float>((hipStream_t)stream, a, lda, b, ldb, out, ldo, rows, C, mode));
 }
 int sr_op_upsample2x_add_f32(const float* lat, const float* top, float* out, int H2, int C, int ld, void* stream) {
-    SR_WRAP(launch_upsample2x_add_f32((hipStream_t)stream, lat, top, out, H2, C, ld));
+    SR_WRAP(launch_upsample2x_add<float>((hipStream_t)stream, lat, top, out, H2, C, ld));
 }
 int sr_op_pixel_shuffle_add_f32(const float* g, int ldg, const float* feat, int ldf, float* out, int ldo, int W, int Co, void* stream) {
-    SR_WRAP(launch_pixel_shuffle_add_f32((hipStream_t)stream, g, ldg, feat, ldf, out, ldo, W, Co));
+    SR_WRAP(launch_pixel_shuffle_add<float>((hipStream_t)stream, g, ldg, feat, ldf, out, ldo, W, Co));
 }
 int sr_op_quant_mx(const void* x, int ldx, int M, int K, void* q, void* scales, int rows_pad, void* stream) {
     SR_WRAP(launch_quant_mx_act((hipStream_t)stream, (const bf16_t*)x, ldx, M, K, (unsigned char*)q, (unsigned char*)scales, rows_pad));

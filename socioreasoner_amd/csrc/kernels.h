@@ -306,24 +306,18 @@ int launch_load2d(hipStream_t s, const void* src, int dtype, long long rows, lon
                   int mode, long long row_off, int tiled);
 
 // ------------------------------------------------------------------ sam.hip (SAM2 image path: the passes between its GEMMs and attention launches)
-int launch_sam_preprocess(hipStream_t s, const uint8_t* img, int h, int w, bf16_t* out_chw, int S);
-int launch_im2col(hipStream_t s, const bf16_t* chw, int S, int k, int stride, int pad, bf16_t* out, int ld, const int* rowmap);
-int launch_layernorm(hipStream_t s, const bf16_t* x, int ldx, const bf16_t* w, const bf16_t* b, bf16_t* out, int ldo, int rows, int C, float eps);
-int launch_maxpool_win(hipStream_t s, const bf16_t* in, int ld_in, int C, int n_win, int ws, bf16_t* out, int ld_out);
-int launch_ew(hipStream_t s, const bf16_t* a, int lda, const bf16_t* b, int ldb, bf16_t* out, int ldo, int rows, int C, int mode);
+// The passes that exist in both storage modes are templates on the element type E, instantiated in sam.hip for bf16_t and float (the reference runs
+// SAM2 in float32; the float32 GEMM / attention: sam_f32.hip below)
+template <typename E> int launch_sam_preprocess(hipStream_t s, const uint8_t* img, int h, int w, E* out_chw, int S);
+template <typename E> int launch_im2col(hipStream_t s, const E* chw, int S, int k, int stride, int pad, E* out, int ld, const int* rowmap);
+template <typename E> int launch_layernorm(hipStream_t s, const E* x, int ldx, const E* w, const E* b, E* out, int ldo, int rows, int C, float eps);
+template <typename E> int launch_maxpool_win(hipStream_t s, const E* in, int ld_in, int C, int n_win, int ws, E* out, int ld_out);
+template <typename E> int launch_ew(hipStream_t s, const E* a, int lda, const E* b, int ldb, E* out, int ldo, int rows, int C, int mode);
+template <typename E> int launch_upsample2x_add(hipStream_t s, const E* lat, const E* top, E* out, int H2, int C, int ld);
+template <typename E> int launch_pixel_shuffle_add(hipStream_t s, const E* g, int ldg, const E* feat, int ldf, E* out, int ldo, int W, int Co);
 int launch_transpose(hipStream_t s, const bf16_t* in, int ld_in, int rows, int cols, bf16_t* out, int ld_out);
-int launch_upsample2x_add(hipStream_t s, const bf16_t* lat, const bf16_t* top, bf16_t* out, int H2, int C, int ld);
-int launch_pixel_shuffle_add(hipStream_t s, const bf16_t* g, int ldg, const bf16_t* feat, int ldf, bf16_t* out, int ldo, int W, int Co);
 int launch_mask_resize_or(hipStream_t s, const float* low, int ld, int col0, int n, int m, const float* score, uint8_t* acc, float* logits_out, int h, int w);
 
-// float32 storage mode of the same passes (the reference runs SAM2 in float32) + the float32 GEMM / attention of sam_f32.hip
-int launch_sam_preprocess_f32(hipStream_t s, const uint8_t* img, int h, int w, float* out_chw, int S);
-int launch_im2col_f32(hipStream_t s, const float* chw, int S, int k, int stride, int pad, float* out, int ld, const int* rowmap);
-int launch_layernorm_f32(hipStream_t s, const float* x, int ldx, const float* w, const float* b, float* out, int ldo, int rows, int C, float eps);
-int launch_maxpool_win_f32(hipStream_t s, const float* in, int ld_in, int C, int n_win, int ws, float* out, int ld_out);
-int launch_ew_f32(hipStream_t s, const float* a, int lda, const float* b, int ldb, float* out, int ldo, int rows, int C, int mode);
-int launch_upsample2x_add_f32(hipStream_t s, const float* lat, const float* top, float* out, int H2, int C, int ld);
-int launch_pixel_shuffle_add_f32(hipStream_t s, const float* g, int ldg, const float* feat, int ldf, float* out, int ldo, int W, int Co);
 // out[M][N] = act(A . W^T + bias) (+ resid), everything float32 row-major; K % 16 == 0, N / lda / ldo % 4 == 0, 16-byte aligned bases
 struct GemmF32Args {
     const float* A; int lda;

@@ -34,33 +34,24 @@ __device__ __forceinline__ void rmsnorm_row_body(bf16_t* x, const bf16_t* xin, c
                 }
         }
     }
-    float v[8] = {lo16(u.x), hi16(u.x), lo16(u.y), hi16(u.y), lo16(u.z), hi16(u.z), lo16(u.w), hi16(u.w)};
+    float v[8];
+    unpack8(u, v);
     if (on && part) {
         float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
-            if (ks < ksplit) {
-                a[0] += p0[ks].x; a[1] += p0[ks].y; a[2] += p0[ks].z; a[3] += p0[ks].w;
-                a[4] += p1[ks].x; a[5] += p1[ks].y; a[6] += p1[ks].z; a[7] += p1[ks].w;
-            }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = rbf(v[e] + rbf(a[e]));
-        *reinterpret_cast<uint4*>(x + (size_t)row * H + c * 8) = uint4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
+            if (ks < ksplit) rms_slab_acc(a, p0[ks], p1[ks]);
+        rms_resid(v, a, x + (size_t)row * H + c * 8);
     }
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ss += v[e] * v[e];
-    ss = wave_sum(ss);
+    const float ss = wave_sum(rms_sumsq(v, 0.f));
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = ss;
     __syncthreads();
-    const float rs = 1.0f / sqrtf((wsum[0] + wsum[1] + wsum[2] + wsum[3]) / (float)H + eps);
+    const float rs = rms_rs(wsum[0] + wsum[1] + wsum[2] + wsum[3], H, eps);
     if (on) {
-        const float wv[8] = {lo16(wu.x), hi16(wu.x), lo16(wu.y), hi16(wu.y), lo16(wu.z), hi16(wu.z), lo16(wu.w), hi16(wu.w)};
         float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = wv[e] * rbf(v[e] * rs);
+        rms_scale(v, wu, rs, o);
         // fragment order: the 8 consecutive k of one row stay contiguous (16 B), see tiled_offset in common.h
         const size_t di = out_tiled ? tiled_offset((size_t)row, (size_t)c * 8, (size_t)H) : (size_t)row * H + c * 8;
-        *reinterpret_cast<uint4*>(out + di) = uint4{pack2(o[0], o[1]), pack2(o[2], o[3]), pack2(o[4], o[5]), pack2(o[6], o[7])};
+        *reinterpret_cast<uint4*>(out + di) = pack8(o);
     }
 }

@@ -1,10 +1,12 @@
 // HBM-bound kernels of the SAM2 (Hiera-L) image path behind seg_infer (SURVEY.md "next" row N1, reference call site
 // /root/reference/roll/distributed/strategy/seg_strategy.py:47-60; arithmetic: transformers/models/sam2/modeling_sam2.py, "hf:").
-// The matrix work of that network runs on the MFMA kernels of gemm.hip / gemm256.hip and on the attention kernels of attention.hip;
-// what is left are coalesced passes over bf16 token matrices [rows][ld] (channel-last, rows padded to whole 64-column k-tiles with
-// zeros so that the next GEMM can consume them as they are), one rounding to bf16 per HF op boundary.
+// The matrix work of that network runs on the MFMA kernels of gemm.hip / gemm256.hip and attention.hip (bf16 storage) or of sam_f32.hip
+// (float32 storage); what is left are coalesced passes over token matrices [rows][ld] (channel-last, rows padded to whole 64-column
+// k-tiles with zeros so that the next GEMM can consume them as they are), one rounding per HF op boundary.  Kernels and launchers are
+// templates on the storage type; kernels.h declares the launchers, the end of this file instantiates them for bf16_t and float.
 #include "kernels.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -15,6 +17,13 @@ __device__ __forceinline__ float ldf(const float* p) { return *p; }
 __device__ __forceinline__ void stf(bf16_t* p, float v) { *p = f2bf(v); }
 __device__ __forceinline__ void stf(float* p, float v) { *p = v; }
 
+// source taps of output index o for a bilinear resize n_in -> n_out with align_corners = False (torch.nn.functional.interpolate):
+// clamped coordinate, its two neighbours and the weight of the second
+__device__ __forceinline__ void bilinear_src(int o, int n_in, int n_out, int& i0, int& i1, float& frac) {
+    const float sc = fmaxf(((float)o + 0.5f) * ((float)n_in / (float)n_out) - 0.5f, 0.f);
+    i0 = min((int)sc, n_in - 1), i1 = min(i0 + 1, n_in - 1), frac = sc - (float)i0;
+}
+
 // ---- predictor pre-processing: uint8 HWC [h][w][3] -> bf16 CHW [3][S][S]: /255, bilinear resize (align_corners = False, as
 // torch.nn.functional.interpolate / torchvision Resize on an upscale), (x - mean) / std
 template <typename T>
@@ -22,9 +31,9 @@ __global__ __launch_bounds__(256) void k_sam_preprocess(const uint8_t* img, int 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= S * S) return;
     const int y = i / S, x = i % S;
-    const float sy = fmaxf(((float)y + 0.5f) * ((float)h / (float)S) - 0.5f, 0.f), sx = fmaxf(((float)x + 0.5f) * ((float)w / (float)S) - 0.5f, 0.f);
-    const int y0 = min((int)sy, h - 1), x0 = min((int)sx, w - 1), y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
-    const float fy = sy - (float)y0, fx = sx - (float)x0;
+    int y0, y1, x0, x1; float fy, fx;
+    bilinear_src(y, h, S, y0, y1, fy);
+    bilinear_src(x, w, S, x0, x1, fx);
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -103,7 +112,8 @@ __global__ __launch_bounds__(256) void k_layernorm_v(const bf16_t* x, int ldx, c
         const int c0 = (l + i * LP) * 8;
         uint4 u = uint4{0, 0, 0, 0};
         if (live && c0 < ldx && c0 < C) u = *reinterpret_cast<const uint4*>(xr + c0);
-        const float t[8] = {lo16(u.x), hi16(u.x), lo16(u.y), hi16(u.y), lo16(u.z), hi16(u.z), lo16(u.w), hi16(u.w)};
+        float t[8];
+        unpack8(u, t);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             v[i][e] = c0 + e < C ? t[e] : 0.f;
@@ -132,16 +142,16 @@ __global__ __launch_bounds__(256) void k_layernorm_v(const bf16_t* x, int ldx, c
         if (c0 >= ldo) continue;
         float o[8];
         if (c0 < C) {
-            const uint4 wu = *reinterpret_cast<const uint4*>(w + c0), bu = *reinterpret_cast<const uint4*>(b + c0);      // (w, b padded to 8 by the caller's layout: C % 8 == 0)
-            const float wf[8] = {lo16(wu.x), hi16(wu.x), lo16(wu.y), hi16(wu.y), lo16(wu.z), hi16(wu.z), lo16(wu.w), hi16(wu.w)};
-            const float bf[8] = {lo16(bu.x), hi16(bu.x), lo16(bu.y), hi16(bu.y), lo16(bu.z), hi16(bu.z), lo16(bu.w), hi16(bu.w)};
+            float wf[8], bf[8];
+            unpack8(*reinterpret_cast<const uint4*>(w + c0), wf);      // (w, b padded to 8 by the caller's layout: C % 8 == 0)
+            unpack8(*reinterpret_cast<const uint4*>(b + c0), bf);
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (v[i][e] - mean) * rstd * wf[e] + bf[e];
         } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = 0.f;
         }
-        *reinterpret_cast<uint4*>(orow + c0) = uint4{pack2(o[0], o[1]), pack2(o[2], o[3]), pack2(o[4], o[5]), pack2(o[6], o[7])};
+        *reinterpret_cast<uint4*>(orow + c0) = pack8(o);
     }
 }
 
@@ -251,9 +261,9 @@ __global__ __launch_bounds__(256) void k_mask_resize_or(const float* low, int ld
     for (int k = 1; k < n; ++k)
         if (score[col0 + k] > score[col0 + best]) best = k;
     const int y = i / w, x = i % w;
-    const float sy = fmaxf(((float)y + 0.5f) * ((float)m / (float)h) - 0.5f, 0.f), sx = fmaxf(((float)x + 0.5f) * ((float)m / (float)w) - 0.5f, 0.f);
-    const int y0 = min((int)sy, m - 1), x0 = min((int)sx, m - 1), y1 = min(y0 + 1, m - 1), x1 = min(x0 + 1, m - 1);
-    const float fy = sy - (float)y0, fx = sx - (float)x0;
+    int y0, y1, x0, x1; float fy, fx;
+    bilinear_src(y, m, h, y0, y1, fy);
+    bilinear_src(x, m, w, x0, x1, fx);
     for (int k = 0; k < n; ++k) {
         if (!logits_out && k != best) continue;
         const int c = col0 + k;
@@ -267,97 +277,77 @@ __global__ __launch_bounds__(256) void k_mask_resize_or(const float* low, int ld
 
 }  // namespace
 
-#define LAUNCH_OK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; return 0; } while (0)
-
-int launch_sam_preprocess(hipStream_t s, const uint8_t* img, int h, int w, bf16_t* out, int S) {
-    hipLaunchKernelGGL(k_sam_preprocess<bf16_t>, dim3(cdiv(S * S, 256)), dim3(256), 0, s, img, h, w, out, S);
-    LAUNCH_OK();
+template <typename E>
+int launch_sam_preprocess(hipStream_t s, const uint8_t* img, int h, int w, E* out, int S) {
+    hipLaunchKernelGGL(k_sam_preprocess<E>, dim3(cdiv(S * S, 256)), dim3(256), 0, s, img, h, w, out, S);
+    SR_CHECK_LAUNCH(); return 0;
 }
-int launch_im2col(hipStream_t s, const bf16_t* chw, int S, int k, int stride, int pad, bf16_t* out, int ld, const int* rowmap) {
+template <typename E>
+int launch_im2col(hipStream_t s, const E* chw, int S, int k, int stride, int pad, E* out, int ld, const int* rowmap) {
     const int T = (S + 2 * pad - k) / stride + 1;
     if (ld < 3 * k * k) return -22;
-    hipLaunchKernelGGL(k_im2col<bf16_t>, dim3(T * T), dim3(256), 0, s, chw, S, k, stride, pad, T, out, ld, rowmap);
-    LAUNCH_OK();
+    hipLaunchKernelGGL(k_im2col<E>, dim3(T * T), dim3(256), 0, s, chw, S, k, stride, pad, T, out, ld, rowmap);
+    SR_CHECK_LAUNCH(); return 0;
 }
-// ---- the float32 storage mode of the same passes (sam_f32.hip holds its GEMM and attention)
-int launch_sam_preprocess_f32(hipStream_t s, const uint8_t* img, int h, int w, float* out, int S) {
-    hipLaunchKernelGGL(k_sam_preprocess<float>, dim3(cdiv(S * S, 256)), dim3(256), 0, s, img, h, w, out, S);
-    LAUNCH_OK();
-}
-int launch_im2col_f32(hipStream_t s, const float* chw, int S, int k, int stride, int pad, float* out, int ld, const int* rowmap) {
-    const int T = (S + 2 * pad - k) / stride + 1;
-    if (ld < 3 * k * k) return -22;
-    hipLaunchKernelGGL(k_im2col<float>, dim3(T * T), dim3(256), 0, s, chw, S, k, stride, pad, T, out, ld, rowmap);
-    LAUNCH_OK();
-}
-int launch_layernorm_f32(hipStream_t s, const float* x, int ldx, const float* w, const float* b, float* out, int ldo, int rows, int C, float eps) {
+template <typename E>
+int launch_layernorm(hipStream_t s, const E* x, int ldx, const E* w, const E* b, E* out, int ldo, int rows, int C, float eps) {
     if (rows <= 0) return 0;
     if (C > 1152 || ldo > 1152) return -22;
-    hipLaunchKernelGGL(k_layernorm<float>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
-    LAUNCH_OK();
+    if constexpr (std::is_same<E, bf16_t>::value) {           // 16 bytes per lane where layout and alignment allow it
+        if (C % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)x | (uintptr_t)out | (uintptr_t)w | (uintptr_t)b) % 16 == 0 && ldo <= 1536) {
+            const int span = ldo > C ? ldo : C;                 // columns a row's lanes must cover (pad columns are written as zeros)
+            if (span <= 256) hipLaunchKernelGGL((k_layernorm_v<32, 1>), dim3(cdiv(rows, 8)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
+            else if (span <= 512) hipLaunchKernelGGL((k_layernorm_v<64, 1>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
+            else if (span <= 1024) hipLaunchKernelGGL((k_layernorm_v<64, 2>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
+            else hipLaunchKernelGGL((k_layernorm_v<64, 3>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
+            SR_CHECK_LAUNCH(); return 0;
+        }
+    }
+    hipLaunchKernelGGL(k_layernorm<E>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
+    SR_CHECK_LAUNCH(); return 0;
 }
-int launch_maxpool_win_f32(hipStream_t s, const float* in, int ld_in, int C, int n_win, int ws, float* out, int ld_out) {
+template <typename E>
+int launch_maxpool_win(hipStream_t s, const E* in, int ld_in, int C, int n_win, int ws, E* out, int ld_out) {
     if (ws % 2) return -22;
-    hipLaunchKernelGGL(k_maxpool_win<float>, dim3(n_win * (ws / 2) * (ws / 2)), dim3(256), 0, s, in, ld_in, C, ws, out, ld_out);
-    LAUNCH_OK();
+    hipLaunchKernelGGL(k_maxpool_win<E>, dim3(n_win * (ws / 2) * (ws / 2)), dim3(256), 0, s, in, ld_in, C, ws, out, ld_out);
+    SR_CHECK_LAUNCH(); return 0;
 }
-int launch_ew_f32(hipStream_t s, const float* a, int lda, const float* b, int ldb, float* out, int ldo, int rows, int C, int mode) {
+template <typename E>
+int launch_ew(hipStream_t s, const E* a, int lda, const E* b, int ldb, E* out, int ldo, int rows, int C, int mode) {
     if (rows <= 0) return 0;
-    hipLaunchKernelGGL(k_ew<float>, dim3((unsigned)(((long long)rows * C + 255) / 256)), dim3(256), 0, s, a, lda, b, ldb, out, ldo, rows, C, mode);
-    LAUNCH_OK();
+    hipLaunchKernelGGL(k_ew<E>, dim3((unsigned)(((long long)rows * C + 255) / 256)), dim3(256), 0, s, a, lda, b, ldb, out, ldo, rows, C, mode);
+    SR_CHECK_LAUNCH(); return 0;
 }
-int launch_upsample2x_add_f32(hipStream_t s, const float* lat, const float* top, float* out, int H2, int C, int ld) {
+template <typename E>
+int launch_upsample2x_add(hipStream_t s, const E* lat, const E* top, E* out, int H2, int C, int ld) {
     if (H2 % 2) return -22;                                 // row H2 / 2 of a top map of H2 / 2 rows (y / 2 of the last row) does not exist
-    hipLaunchKernelGGL(k_upsample2x_add<float>, dim3((unsigned)(((long long)H2 * H2 * C + 255) / 256)), dim3(256), 0, s, lat, top, out, H2, C, ld);
-    LAUNCH_OK();
+    hipLaunchKernelGGL(k_upsample2x_add<E>, dim3((unsigned)(((long long)H2 * H2 * C + 255) / 256)), dim3(256), 0, s, lat, top, out, H2, C, ld);
+    SR_CHECK_LAUNCH(); return 0;
 }
-int launch_pixel_shuffle_add_f32(hipStream_t s, const float* g, int ldg, const float* feat, int ldf, float* out, int ldo, int W, int Co) {
-    hipLaunchKernelGGL(k_pixel_shuffle_add<float>, dim3((unsigned)((4ll * W * W * Co + 255) / 256)), dim3(256), 0, s, g, ldg, feat, ldf, out, ldo, W, Co);
-    LAUNCH_OK();
+template <typename E>
+int launch_pixel_shuffle_add(hipStream_t s, const E* g, int ldg, const E* feat, int ldf, E* out, int ldo, int W, int Co) {
+    hipLaunchKernelGGL(k_pixel_shuffle_add<E>, dim3((unsigned)((4ll * W * W * Co + 255) / 256)), dim3(256), 0, s, g, ldg, feat, ldf, out, ldo, W, Co);
+    SR_CHECK_LAUNCH(); return 0;
 }
-int launch_layernorm(hipStream_t s, const bf16_t* x, int ldx, const bf16_t* w, const bf16_t* b, bf16_t* out, int ldo, int rows, int C, float eps) {
-    if (rows <= 0) return 0;
-    if (C > 1152 || ldo > 1152) return -22;
-    const bool vec = C % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)x | (uintptr_t)out | (uintptr_t)w | (uintptr_t)b) % 16 == 0 && ldo <= 1536;
-    if (vec) {
-        const int span = ldo > C ? ldo : C;                 // columns a row's lanes must cover (pad columns are written as zeros)
-        if (span <= 256) hipLaunchKernelGGL((k_layernorm_v<32, 1>), dim3(cdiv(rows, 8)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
-        else if (span <= 512) hipLaunchKernelGGL((k_layernorm_v<64, 1>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
-        else if (span <= 1024) hipLaunchKernelGGL((k_layernorm_v<64, 2>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
-        else hipLaunchKernelGGL((k_layernorm_v<64, 3>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
-        LAUNCH_OK();
-    }
-    hipLaunchKernelGGL(k_layernorm<bf16_t>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, b, out, ldo, rows, C, eps);
-    LAUNCH_OK();
-}
-int launch_maxpool_win(hipStream_t s, const bf16_t* in, int ld_in, int C, int n_win, int ws, bf16_t* out, int ld_out) {
-    if (ws % 2) return -22;
-    hipLaunchKernelGGL(k_maxpool_win<bf16_t>, dim3(n_win * (ws / 2) * (ws / 2)), dim3(256), 0, s, in, ld_in, C, ws, out, ld_out);
-    LAUNCH_OK();
-}
-int launch_ew(hipStream_t s, const bf16_t* a, int lda, const bf16_t* b, int ldb, bf16_t* out, int ldo, int rows, int C, int mode) {
-    if (rows <= 0) return 0;
-    hipLaunchKernelGGL(k_ew<bf16_t>, dim3((unsigned)(((long long)rows * C + 255) / 256)), dim3(256), 0, s, a, lda, b, ldb, out, ldo, rows, C, mode);
-    LAUNCH_OK();
-}
+// the two storage modes of the passes above (the float32 one is the reference's own precision for SAM2; its GEMM and attention: sam_f32.hip)
+#define SR_SAM_INSTANTIATE(E)                                                                                                                 \
+    template int launch_sam_preprocess<E>(hipStream_t, const uint8_t*, int, int, E*, int);                                                    \
+    template int launch_im2col<E>(hipStream_t, const E*, int, int, int, int, E*, int, const int*);                                            \
+    template int launch_layernorm<E>(hipStream_t, const E*, int, const E*, const E*, E*, int, int, int, float);                               \
+    template int launch_maxpool_win<E>(hipStream_t, const E*, int, int, int, int, E*, int);                                                   \
+    template int launch_ew<E>(hipStream_t, const E*, int, const E*, int, E*, int, int, int, int);                                             \
+    template int launch_upsample2x_add<E>(hipStream_t, const E*, const E*, E*, int, int, int);                                                \
+    template int launch_pixel_shuffle_add<E>(hipStream_t, const E*, int, const E*, int, E*, int, int, int);
+SR_SAM_INSTANTIATE(bf16_t)
+SR_SAM_INSTANTIATE(float)
+
 int launch_transpose(hipStream_t s, const bf16_t* in, int ld_in, int rows, int cols, bf16_t* out, int ld_out) {
-    if (cols % 8 == 0 && ld_in % 8 == 0 && ld_out % 8 == 0 && ((uintptr_t)in | (uintptr_t)out) % 16 == 0) {
+    if (cols % 8 == 0 && ld_in % 8 == 0 && ld_out % 8 == 0 && ((uintptr_t)in | (uintptr_t)out) % 16 == 0)
         hipLaunchKernelGGL(k_transpose_v, dim3(cdiv(rows, 64), cdiv(cols, 64)), dim3(256), 0, s, in, ld_in, rows, cols, out, ld_out);
-        LAUNCH_OK();
-    }
-    hipLaunchKernelGGL(k_transpose, dim3(cdiv(rows, 32), cdiv(cols, 32)), dim3(256), 0, s, in, ld_in, rows, cols, out, ld_out);
-    LAUNCH_OK();
-}
-int launch_upsample2x_add(hipStream_t s, const bf16_t* lat, const bf16_t* top, bf16_t* out, int H2, int C, int ld) {
-    if (H2 % 2) return -22;
-    hipLaunchKernelGGL(k_upsample2x_add<bf16_t>, dim3((unsigned)(((long long)H2 * H2 * C + 255) / 256)), dim3(256), 0, s, lat, top, out, H2, C, ld);
-    LAUNCH_OK();
-}
-int launch_pixel_shuffle_add(hipStream_t s, const bf16_t* g, int ldg, const bf16_t* feat, int ldf, bf16_t* out, int ldo, int W, int Co) {
-    hipLaunchKernelGGL(k_pixel_shuffle_add<bf16_t>, dim3((unsigned)((4ll * W * W * Co + 255) / 256)), dim3(256), 0, s, g, ldg, feat, ldf, out, ldo, W, Co);
-    LAUNCH_OK();
+    else hipLaunchKernelGGL(k_transpose, dim3(cdiv(rows, 32), cdiv(cols, 32)), dim3(256), 0, s, in, ld_in, rows, cols, out, ld_out);
+    SR_CHECK_LAUNCH(); return 0;
 }
 int launch_mask_resize_or(hipStream_t s, const float* low, int ld, int col0, int n, int m, const float* score, uint8_t* acc, float* logits_out, int h, int w) {
     hipLaunchKernelGGL(k_mask_resize_or, dim3(cdiv(h * w, 256)), dim3(256), 0, s, low, ld, col0, n, m, score, acc, logits_out, h, w);
-    LAUNCH_OK();
+    SR_CHECK_LAUNCH(); return 0;
 }

@@ -28,6 +28,67 @@ namespace {
 // at ~25 % of its cycles).
 constexpr int GB = 128, GK = 16, GP = GB + 4;
 
+// epilogue: D[n][m], lane (kg, col): m = col, n = 8 * (v / 4) + 4 * kg + v % 4.
+// Instantiated per (bias, residual, activation) case behind block-uniform branches.  The residual may alias the output (the blocks add
+// in place), so inside one store loop every residual load waited for the previous store: the four float4s of a (row group, column
+// half) are fetched together, ahead of its stores -- four round trips per tile instead of sixteen.  (All sixteen up front cost 86 more
+// registers and two of the four blocks a CU holds: batched encoder 156 -> 164 ms.  With four blocks per CU the others' k loops hide what
+// is left.)  Same arithmetic, same order.
+__device__ __forceinline__ void gemm_f32_epilogue(const GemmF32Args& p, const f32x16 (&acc)[2][2], int m0, int n0, int wm, int wn, int kg, int col) {
+    auto epilogue = [&](auto hb_, auto hr_, auto act_) {
+        constexpr bool HB = decltype(hb_)::value, HR = decltype(hr_)::value;
+        constexpr int ACT = decltype(act_)::value;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int m = m0 + wm * 64 + i * 32 + col;
+            if (m >= p.M) continue;
+            const size_t orow = (size_t)(p.rowmap ? p.rowmap[m] : m) * p.ldo;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                float4 rv[4];
+                if constexpr (HR) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int n = n0 + wn * 64 + j * 32 + 8 * q + 4 * kg;
+                        rv[q] = n < p.N ? *reinterpret_cast<const float4*>(p.resid + orow + n) : float4{0.f, 0.f, 0.f, 0.f};
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int n = n0 + wn * 64 + j * 32 + 8 * q + 4 * kg;
+                    if (n >= p.N) continue;
+                    float o[4];
+                    float4 bq = float4{0.f, 0.f, 0.f, 0.f};
+                    if constexpr (HB) bq = *reinterpret_cast<const float4*>(p.bias + n);
+                    const float bb[4] = {bq.x, bq.y, bq.z, bq.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float x = acc[j][i][4 * q + e];
+                        if constexpr (HB) x += bb[e];
+                        if constexpr (ACT == 1) x = gelu_f(x);
+                        else if constexpr (ACT == 2) x = fmaxf(x, 0.f);
+                        o[e] = x;
+                    }
+                    if constexpr (HR) {
+                        const float4 r = rv[q];
+                        o[0] = r.x + o[0]; o[1] = r.y + o[1]; o[2] = r.z + o[2]; o[3] = r.w + o[3];
+                    }
+                    *reinterpret_cast<float4*>(p.out + orow + n) = float4{o[0], o[1], o[2], o[3]};
+                }
+            }
+        }
+    };
+    using T_ = std::true_type;
+    using F_ = std::false_type;
+    auto by_act = [&](auto hb_, auto hr_) {
+        if (p.act == 1) epilogue(hb_, hr_, std::integral_constant<int, 1>{});
+        else if (p.act == 2) epilogue(hb_, hr_, std::integral_constant<int, 2>{});
+        else epilogue(hb_, hr_, std::integral_constant<int, 0>{});
+    };
+    if (p.bias) { if (p.resid) by_act(T_{}, T_{}); else by_act(T_{}, F_{}); }
+    else { if (p.resid) by_act(F_{}, T_{}); else by_act(F_{}, F_{}); }
+}
+
 __global__ __launch_bounds__(256, 2) void k_gemm_f32(GemmF32Args p, int n_tiles_n) {
     __shared__ float As[2][GK][GP];
     __shared__ float Ws[2][GK][GP];
@@ -94,64 +155,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(GemmF32Args p, int n_tiles_
         if (kt + 1 < nk) lstore(cur ^ 1);
         __syncthreads();
     }
-    // epilogue: D[n][m], lane (kg, col): m = col, n = 8 * (v / 4) + 4 * kg + v % 4.
-    // Instantiated per (bias, residual, activation) case behind block-uniform branches.  The residual may alias the output (the blocks add
-    // in place), so inside one store loop every residual load waited for the previous store: the four float4s of a (row group, column
-    // half) are fetched together, ahead of its stores -- four round trips per tile instead of sixteen.  (All sixteen up front cost 86 more
-    // registers and two of the four blocks a CU holds: batched encoder 156 -> 164 ms.  With four blocks per CU the others' k loops hide what
-    // is left.)  Same arithmetic, same order.
-    auto epilogue = [&](auto hb_, auto hr_, auto act_) {
-        constexpr bool HB = decltype(hb_)::value, HR = decltype(hr_)::value;
-        constexpr int ACT = decltype(act_)::value;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = m0 + wm * 64 + i * 32 + col;
-            if (m >= p.M) continue;
-            const size_t orow = (size_t)(p.rowmap ? p.rowmap[m] : m) * p.ldo;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                float4 rv[4];
-                if constexpr (HR) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int n = n0 + wn * 64 + j * 32 + 8 * q + 4 * kg;
-                        rv[q] = n < p.N ? *reinterpret_cast<const float4*>(p.resid + orow + n) : float4{0.f, 0.f, 0.f, 0.f};
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int n = n0 + wn * 64 + j * 32 + 8 * q + 4 * kg;
-                    if (n >= p.N) continue;
-                    float o[4];
-                    float4 bq = float4{0.f, 0.f, 0.f, 0.f};
-                    if constexpr (HB) bq = *reinterpret_cast<const float4*>(p.bias + n);
-                    const float bb[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = acc[j][i][4 * q + e];
-                        if constexpr (HB) x += bb[e];
-                        if constexpr (ACT == 1) x = gelu_f(x);
-                        else if constexpr (ACT == 2) x = fmaxf(x, 0.f);
-                        o[e] = x;
-                    }
-                    if constexpr (HR) {
-                        const float4 r = rv[q];
-                        o[0] = r.x + o[0]; o[1] = r.y + o[1]; o[2] = r.z + o[2]; o[3] = r.w + o[3];
-                    }
-                    *reinterpret_cast<float4*>(p.out + orow + n) = float4{o[0], o[1], o[2], o[3]};
-                }
-            }
-        }
-    };
-    using T_ = std::true_type;
-    using F_ = std::false_type;
-    auto by_act = [&](auto hb_, auto hr_) {
-        if (p.act == 1) epilogue(hb_, hr_, std::integral_constant<int, 1>{});
-        else if (p.act == 2) epilogue(hb_, hr_, std::integral_constant<int, 2>{});
-        else epilogue(hb_, hr_, std::integral_constant<int, 0>{});
-    };
-    if (p.bias) { if (p.resid) by_act(T_{}, T_{}); else by_act(T_{}, F_{}); }
-    else { if (p.resid) by_act(F_{}, T_{}); else by_act(F_{}, F_{}); }
+    gemm_f32_epilogue(p, acc, m0, n0, wm, wn, kg, col);
 }
 
 // ------------------------------------------------------------------------------------------------ GEMM on the bf16 matrix pipe (round 5)
@@ -167,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(GemmF32Args p, int n_tiles_
 // whose summation order differs from ours anyway) carries: tests/test_gpu_round4.py::test_gemm_f32_vs_float64 holds this kernel to the bound
 // it held the f32-input kernel to, and SAM2's masks keep their pixel-exactness against HF float32 (tests/test_gpu_sam2.py).
 // 6 x v_mfma_f32_32x32x16_bf16 (32 cycles each) replace 8 x v_mfma_f32_32x32x2_f32 (64 cycles each) per 16 k: 2.67 x fewer matrix-pipe cycles.
-// Tiles as above (128 x 128 x 16, 4 waves 2 x 2, D = W_frag x A_frag -> the same accumulator layout and epilogue).  The split happens on the
+// Tiles as above (128 x 128 x 16, 4 waves 2 x 2, D = W_frag x A_frag -> the same accumulator layout, gemm_f32_epilogue).  The split happens on the
 // way from global memory to LDS: thread t owns 8 consecutive k of one row (row t / 2, k half t % 2) of each operand; LDS holds three bf16
 // planes per operand as [k half][row][8 k] (16 bytes per entry: fragment reads are conflict-free ds_read_b128, stores conflict-free
 // ds_write_b128 with the second k half displaced by 64 bytes).
@@ -301,59 +305,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32s(GemmF32Args p, int n_tiles
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int v = 0; v < 16; ++v) acc[j][i][v] += cor[j][i][v];
-    // epilogue: identical to k_gemm_f32's (same accumulator layout)
-    auto epilogue = [&](auto hb_, auto hr_, auto act_) {
-        constexpr bool HB = decltype(hb_)::value, HR = decltype(hr_)::value;
-        constexpr int ACT = decltype(act_)::value;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = m0 + wm * 64 + i * 32 + col;
-            if (m >= p.M) continue;
-            const size_t orow = (size_t)(p.rowmap ? p.rowmap[m] : m) * p.ldo;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                float4 rv[4];
-                if constexpr (HR) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int n = n0 + wn * 64 + j * 32 + 8 * q + 4 * kg;
-                        rv[q] = n < p.N ? *reinterpret_cast<const float4*>(p.resid + orow + n) : float4{0.f, 0.f, 0.f, 0.f};
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int n = n0 + wn * 64 + j * 32 + 8 * q + 4 * kg;
-                    if (n >= p.N) continue;
-                    float o[4];
-                    float4 bq = float4{0.f, 0.f, 0.f, 0.f};
-                    if constexpr (HB) bq = *reinterpret_cast<const float4*>(p.bias + n);
-                    const float bb[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = acc[j][i][4 * q + e];
-                        if constexpr (HB) x += bb[e];
-                        if constexpr (ACT == 1) x = gelu_f(x);
-                        else if constexpr (ACT == 2) x = fmaxf(x, 0.f);
-                        o[e] = x;
-                    }
-                    if constexpr (HR) {
-                        const float4 r = rv[q];
-                        o[0] = r.x + o[0]; o[1] = r.y + o[1]; o[2] = r.z + o[2]; o[3] = r.w + o[3];
-                    }
-                    *reinterpret_cast<float4*>(p.out + orow + n) = float4{o[0], o[1], o[2], o[3]};
-                }
-            }
-        }
-    };
-    using T_ = std::true_type;
-    using F_ = std::false_type;
-    auto by_act = [&](auto hb_, auto hr_) {
-        if (p.act == 1) epilogue(hb_, hr_, std::integral_constant<int, 1>{});
-        else if (p.act == 2) epilogue(hb_, hr_, std::integral_constant<int, 2>{});
-        else epilogue(hb_, hr_, std::integral_constant<int, 0>{});
-    };
-    if (p.bias) { if (p.resid) by_act(T_{}, T_{}); else by_act(T_{}, F_{}); }
-    else { if (p.resid) by_act(F_{}, T_{}); else by_act(F_{}, F_{}); }
+    gemm_f32_epilogue(p, acc, m0, n0, wm, wn, kg, col);
 }
 
 // ------------------------------------------------------------------------------------------------ attention
