@@ -270,6 +270,35 @@ int sr_rows_per_row(sr_engine* e, int on, void* stream);
 int sr_rows_step(sr_engine* e, int n_steps, const int32_t* host_eos, int n_eos, int32_t pad_id, void* stream);
 int sr_rows_poll(sr_engine* e, int32_t* host_finished, int32_t* host_steps, void* stream);
 int sr_rows_read(sr_engine* e, int row, int32_t* dev_tokens_out, int n, void* stream);
+
+/* Token log-probs (vLLM's SamplingParams.logprobs = N with raw log-probs; the reference asks logprobs=0 for every rollout,
+ * roll/distributed/strategy/vllm_strategy.py:289-309): the engine records, in the step that picks a token, the log-prob of that token and
+ * optionally the row's N most likely tokens.
+ *   For every generated token of a sequence, with x the float32 logits row that produced it exactly as the LM head stored it:
+ *     lp = x[tok] - logsumexp(x)   -- no temperature, no repetition penalty, no top-k / top-p truncation (with temperature 1 and no penalty
+ *                                     that is the log-prob under the distribution the token was drawn from before truncation);
+ *     top_n = N > 0: the N largest logits of the row ordered by (logit descending, token id ascending), stored as top_ids[N] int32 and
+ *                                     top_lp[N] = x[id] - logsumexp(x).  The top arrays always have 8 entries per record: ids past N are -1,
+ *                                     their log-probs 0.
+ *   A record exists for every logged token of a live row, eos included.  Position 0 comes from the prefill / admission logits (a fork of a
+ *   fan-out admission: its prompt's logits row and its own first token; staged sequences carry it until sr_admit_commit installs them).
+ *   Positions a static decode pads after a row finished hold lp = 0, top_ids = -1, top_lp = 0, and a row never shows records of its
+ *   previous occupant (an admission clears the rest of its row's log).  Greedy rows: top_ids[0] == tok and top_lp[0] == lp bit for bit.
+ *   Under teacher forcing (sr_decode's `forced`) the logged token is the arg-max, and so is its record.
+ *   Deterministic: every reduction runs in a fixed order and a token's record depends only on its logits row -- not on the batch size, the
+ *   row index, the neighbours, graph replay or eager launches, sr_rows_set_cus, or overlapped / plain admission.  NaN logits are outside
+ *   the contract; -inf logits are allowed (lp may be -inf); nothing overflows for logits of magnitude 80.
+ *   Recorded by sr_decode, sr_decode_sample and sr_rows_step (shared greedy, shared sampled, per-row) inside their captured step, and by
+ *   the admissions.  NOT recorded by sr_decode_beam (its scores already are summed log-probs) and sr_decode_step (the caller holds the
+ *   logits).  With the switch off (the default) every captured step holds exactly the launches it held before.
+ *   sr_logprobs : top_n -1 = off, 0..8 = record with that N from the next step / admission / decode on; anything else is refused (-22, the
+ *                 value named).  May be called between any two steps or calls; records are written under the N in force.  The first
+ *                 call that switches on allocates the log outside the workspace (max_batch x max_new_tokens records laid out for N = 8,
+ *                 cleared), so sr_workspace_bytes and sr_config are unchanged.
+ *   sr_rows_read_logprobs : the first n records of a row, device to device: dev_lp float32 [n], and (each optional) dev_top_ids int32
+ *                 [n][8], dev_top_lp float32 [n][8].  After sr_decode / sr_decode_sample, row = batch index. */
+int sr_logprobs(sr_engine* e, int top_n, void* stream);
+int sr_rows_read_logprobs(sr_engine* e, int row, float* dev_lp, int32_t* dev_top_ids, float* dev_top_lp, int n, void* stream);
 int sr_rows_abort(sr_engine* e, const int32_t* host_rows, int n, void* stream);
 int sr_rows_set_cus(sr_engine* e, int n_cus, void* stream);
 
@@ -448,6 +477,14 @@ int sr_op_rmsnorm(const void* x, const void* w, void* out, int rows, int H, floa
 int sr_op_resid_rmsnorm(void* x, const float* partials, int ksplit, const void* w, void* out, int rows, int H, float eps,
                         void* stream);
 int sr_op_argmax(const float* logits, int rows, int V, int32_t* out_idx, void* stream);
+/* the log-prob kernels of sr_logprobs alone, on caller-provided buffers: record i (0 <= i < rows <= 128) reads the float32 logits row
+ * row_map[i] (int32, device; null: i) of `logits` (leading dimension ld >= V >= 16; columns V .. ld are never read) and the token
+ * dev_tokens[i] (int64, device; null: the arg-max, lowest id among the maxima) -> lp [rows], tok_out int32 [rows] (optional), top_ids int32
+ * [rows][8] and top_lp [rows][8] (optional, both or neither; entries past top_n hold -1 / 0).  0 <= top_n <= 8.  Nothing else is written.
+ * NOT thread-safe: the call keeps one process-wide scratch buffer for the chunk partials, grown (after a device synchronize) when a call needs more;
+ * call it from one thread at a time and on one device. */
+int sr_op_token_logprobs(const float* logits, int64_t ld, int rows, int V, const int64_t* dev_tokens, const int32_t* row_map, int top_n, float* lp,
+                         int32_t* tok_out, int32_t* top_ids, float* top_lp, void* stream);
 /* the fan-out kernel of sr_admit_stage_fanout on caller-provided caches kcache [layer][slot][kvh][max_ctx][128], vtcache
  * [layer][slot][kvh][128][max_ctx] (layer_stride_elems elements from one layer to the next in each): positions [0, L) of slot src_slot ->
  * slots dev_dst_slots[0..d) (int32, device), all layers, one launch; nothing else is written.  max_ctx % 64 == 0. */

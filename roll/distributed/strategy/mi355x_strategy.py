@@ -347,6 +347,7 @@ class Mi355xStrategy(InferenceStrategy):
         W = int(gc.get("num_beams", 1) or 1)
         if W > 1:
             check_beam_config(gc, self.engine.cfg.max_batch)
+        lpn = check_logprobs_config(gc)
         greedy = sampling.is_greedy(gc) and float(gc.get("repetition_penalty", 1.0) or 1.0) == 1.0
         n = int(gc.get("num_return_sequences", 1) or 1)
         input_ids = batch.batch["input_ids"]
@@ -397,7 +398,7 @@ class Mi355xStrategy(InferenceStrategy):
                     raise ValueError(f"prompt of {len(ids_k)} tokens leaves no room in max_ctx {self.engine.cfg.max_ctx}")
                 for c0 in range(0, fan, mb):
                     reqs.append(Request(ids=ids_k, pos3=pos_k, max_new=max(1, min(max_new, room)), images=ims_k, grids=grids_k, n=min(mb, fan - c0),
-                                        sampling=own))
+                                        sampling=own, logprobs=lpn))
                     owner.append(k)
             t_run0 = _time.perf_counter()
             cb = ContinuousBatcher(self.engine, eos, pad, sampling=smp, overlap=self.overlap)
@@ -409,13 +410,22 @@ class Mi355xStrategy(InferenceStrategy):
                                                "poll_wait_ms", "shares", "share_model")}})
             for k in range(B):
                 results[k] = []
+            recs = [[] for _ in range(B)]             # with logprobs: every response's records, cut like its tokens
             for k, r, out in zip(owner, reqs, outs):
-                for row in (out if r.n > 1 else [out]):
+                for j, row in enumerate(out if r.n > 1 else [out]):
                     row = [int(t) for t in row]
                     cut = next((j + 1 for j, t in enumerate(row) if t in eos), len(row))
                     results[k].append(row[:cut])
+                    if lpn is not None:
+                        rec = r.out_logprobs[j] if r.n > 1 else r.out_logprobs
+                        recs[k].append((rec["logprobs"][:cut], rec["top"][:cut]))
             if g0:
                 results = [rs * n for rs in results]
+                recs = [rs * n for rs in recs]
+            if lpn is not None:                        # one entry per row of the returned tensor, in its row order
+                batch.meta_info["output_logprobs"] = [lp for rs in recs for lp, _ in rs]
+                if lpn > 0:
+                    batch.meta_info["output_top_logprobs"] = [top for rs in recs for _, top in rs]
             i = B
         while i < B:                                  # static batches (sampling with top-k above 1024)
             grp, ntok, npatch = [], 0, 0
@@ -568,6 +578,7 @@ class Mi355xStrategy(InferenceStrategy):
                     dev_sampling = not greedy and tk <= 1024 and float(gc.get("temperature", 1.0)) > 1e-5
                     n_req = int(gc.get("num_return_sequences", 1) or 1)
                     rp = float(gc.get("repetition_penalty", 1.0) or 1.0)
+                    lpn = check_logprobs_config(gc)
                     rows_ok = (hasattr(self.engine, "rows_begin") and (greedy or dev_sampling) and rp > 0
                                and n_req <= getattr(getattr(self.engine, "cfg", None), "max_batch", 1)
                                and int(gc.get("num_beams", 1) or 1) == 1)          # beam search: the static path (generate's beam branch)
@@ -585,6 +596,8 @@ class Mi355xStrategy(InferenceStrategy):
                         # a new batcher (its shared configuration = this request's) only when none runs; a running one takes requests with other
                         # sampling parameters into its rows, each under its own parameters (the per-row step)
                         if batcher is None or (batcher.idle() and (key, dkey) != (bkey, bdkey)):
+                            if batcher is not None:
+                                batcher._hand_back()      # (the engine's log-prob recording off again before the batcher goes)
                             batcher, bkey, bdkey = ContinuousBatcher(self.engine, eos, pad, sampling=smp, overlap=self.overlap), key, dkey
                         if key != bkey:
                             sampled.append(req)          # a different stop set / pad id while rows are running: static path
@@ -609,7 +622,7 @@ class Mi355xStrategy(InferenceStrategy):
                                 raise ValueError(f"prompt of {len(ids)} tokens leaves no room in max_ctx {self.engine.cfg.max_ctx}")
                             max_new = max(1, min(int(gc["max_new_tokens"]), self.engine.cfg.max_new_tokens, room))
                             batcher.submit(Request(ids=ids, pos3=pos3, max_new=max_new, images=ims, grids=grids, tag=req,
-                                                   n=1 if greedy else n_req, sampling=own))          # (greedy: the n answers are one answer)
+                                                   n=1 if greedy else n_req, sampling=own, logprobs=lpn))          # (greedy: the n answers are one answer)
                 elif name == "ABORT":
                     rid = req.meta_info["request_id"]
                     sampled = [p for p in sampled if p.meta_info.get("request_id") != rid]
@@ -637,6 +650,11 @@ class Mi355xStrategy(InferenceStrategy):
                     n_out = int((r.tag.meta_info.get("generation_config") or {}).get("num_return_sequences", 1) or 1)
                     lists = toks if r.n > 1 else [toks] * n_out
                     res.meta_info["output_token_ids"] = [[int(t) for t in x] for x in lists]
+                    if r.logprobs is not None:      # next to the tokens, one entry per token list
+                        recs = r.out_logprobs if r.n > 1 else [r.out_logprobs] * n_out
+                        res.meta_info["output_logprobs"] = [list(x["logprobs"]) for x in recs]
+                        if r.logprobs > 0:
+                            res.meta_info["output_top_logprobs"] = [list(x["top"]) for x in recs]
                     request_complete_callback(data=res)
                 batcher.pump(done)
             if sampled and (len(sampled) >= self.max_batch or self.command_queue.empty()):
@@ -646,10 +664,16 @@ class Mi355xStrategy(InferenceStrategy):
                     same = [r for r in todo if r.meta_info.get("generation_config") == gc]
                     sampled = [r for r in todo if r.meta_info.get("generation_config") != gc] + sampled
                     todo = same
+                # one generate call runs under ONE config: requests that ask for other log-probs (or none) than the first wait for a batch of their own
+                lp_of = lambda r: (r.meta_info.get("generation_config") or {}).get("logprobs")
+                sampled = [r for r in todo if lp_of(r) != lp_of(todo[0])] + sampled
+                todo = [r for r in todo if lp_of(r) == lp_of(todo[0])]
                 if batcher is not None and not batcher.idle():
                     sampled = todo + sampled      # rows are running: the static path needs the whole engine, wait
                 else:
                     merged = DataProto.concat(todo)
+                    if batcher is not None:
+                        batcher._hand_back()          # (the engine's log-prob recording off again before the batcher goes)
                     out = self.generate(merged, gc)
                     batcher = None                # generate() re-initialises the batch rows
                     P = merged.batch["input_ids"].shape[1]
@@ -658,14 +682,39 @@ class Mi355xStrategy(InferenceStrategy):
                         res = DataProto(meta_info=dict(r.meta_info))
                         res.meta_info["output_token_ids"] = [[int(t) for t in row[P:].tolist() if int(t) != int(gc.get("pad_token_id", -1))]
                                                              for row in out[i_r * n_out:(i_r + 1) * n_out]]
+                        for key in ("output_logprobs", "output_top_logprobs"):      # generate() recorded them per row of `out`
+                            if key in merged.meta_info:
+                                res.meta_info[key] = merged.meta_info[key][i_r * n_out:(i_r + 1) * n_out]
                         request_complete_callback(data=res)
             if stop and (batcher is None or batcher.idle()) and not sampled:
                 self.running = False
+                if batcher is not None:
+                    batcher._hand_back()
                 if batcher is not None and hasattr(self, "gen_stats"):      # (as generate(): what the scheduler did while this server was open)
                     self.gen_stats.append({"requests": batcher.stats["admitted"], "served_as": "request stream",
                                            **{k: (round(v, 1) if isinstance(v, float) else v) for k, v in batcher.stats.items()
                                               if k in ("steps", "steps_shared", "admissions", "rounds", "host_ms", "poll_wait_ms", "shares", "share_model")}})
                 return
+
+
+def check_logprobs_config(gc: dict):
+    """generation_config["logprobs"]: absent / None = off (-> None), N in 0..8 = the log-prob of every response token under the raw logits and
+    the N most likely tokens of its step (vLLM's SamplingParams.logprobs; the engine records them in the step that picks the token).  What
+    the engine does not record is refused by name."""
+    lp = gc.get("logprobs")
+    if lp is None:
+        return None
+    if isinstance(lp, bool) or int(lp) != lp or not 0 <= int(lp) <= 8:
+        raise ValueError(f"logprobs={lp!r} is outside the engine's range 0..8 (top-N entries per token)")
+    W = int(gc.get("num_beams", 1) or 1)
+    if W > 1:
+        raise NotImplementedError(f"logprobs={lp} together with num_beams={W} is not supported (beam search returns summed log-probs as its scores)")
+    tk = gc.get("top_k", -1)
+    tk = -1 if tk is None else int(tk)
+    if tk > 1024 and not sampling.is_greedy(gc):
+        raise NotImplementedError(f"logprobs={lp} together with top_k={tk} > 1024 is not supported (that draw runs on the host, outside the "
+                                  "step that records log-probs)")
+    return int(lp)
 
 
 def check_beam_config(gc: dict, max_batch: int):

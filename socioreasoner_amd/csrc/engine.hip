@@ -119,8 +119,9 @@ struct StepKey {
     int B, n_eos, pad_id;
     int top_k; float inv_temp, top_p, rep_penalty; unsigned seed;      // the sampled kinds
     int W, K, max_new; float length_penalty;                           // beam
+    int lp;                                                            // token log-probs (sr_logprobs): top_n + 1 when the step records them, 0 = off
 };
-static_assert(sizeof(StepKey) == 12 * 4, "no padding");
+static_assert(sizeof(StepKey) == 13 * 4, "no padding");
 struct StepGraph { hipGraphExec_t exec = nullptr; StepKey key{}; };
 
 struct sr_engine {
@@ -208,6 +209,13 @@ struct sr_engine {
     void* beam_mem = nullptr;
     BeamPart* bm_part = nullptr; float* bm_scores = nullptr; long long* bm_tok = nullptr; BeamTrace* bm_trace = nullptr; BeamFin* bm_fin = nullptr;
     int *bm_fin_n = nullptr, *bm_done = nullptr, *bm_stop = nullptr, *bm_eos = nullptr, *bm_plen = nullptr, *bm_fan = nullptr; int4* bm_copies = nullptr;
+    // token log-probs (sr_logprobs): allocated on first use, freed on destroy.  lp_n: -1 = off, else the top_n in force.  lp_log / lp_ids /
+    // lp_tlp: the log [max_batch][max_new_tokens] (x LP_MAXN); lps_*: the position-0 records of the staged sequences [MAXB]; lp_part /
+    // lp_part_adm: chunk partials of the decode step / of an admission (which may run on another stream under the steps)
+    void* lp_mem = nullptr; int lp_n = -1;
+    float *lp_log = nullptr, *lp_tlp = nullptr, *lps_lp = nullptr, *lps_tlp = nullptr; int *lp_ids = nullptr, *lps_ids = nullptr;
+    BeamPart *lp_part = nullptr, *lp_part_adm = nullptr;
+    bool staged_lp = false;        // the staged admission recorded its first tokens
     int h_ctx_hi = 0;              // longest context any slot can have reached (prefill length + decode steps issued)
     // ---- bookkeeping
     std::map<std::string, bool> loaded;
@@ -822,9 +830,12 @@ Step make_step(int B, int n_eos, int pad_id, const long long* chosen) {
     st.B = B; st.n_eos = n_eos; st.pad_id = pad_id; st.chosen = chosen;
     return st;
 }
-StepKey step_key(const Step& st) {
+// the steps that pick their tokens themselves record log-probs under sr_logprobs (beam search and sr_decode_step do not)
+bool step_records(const sr_engine* e, const Step& st) { return e->lp_n >= 0 && (st.tail == Step::TAIL_NONE || st.tail == Step::TAIL_SAMPLE); }
+StepKey step_key(const sr_engine* e, const Step& st) {
     StepKey k{};
     k.B = st.B; k.n_eos = st.n_eos; k.pad_id = st.pad_id;
+    k.lp = step_records(e, st) ? e->lp_n + 1 : 0;
     if (st.tail == Step::TAIL_SAMPLE) {
         k.top_k = st.sample.top_k; k.inv_temp = st.sample.inv_temp; k.top_p = st.sample.top_p; k.rep_penalty = st.sample.rep_penalty; k.seed = st.sample.seed;
     } else if (st.tail == Step::TAIL_BEAM) {      // (k_step runs without eos there: the select kernel owns them)
@@ -843,6 +854,11 @@ int enqueue_step_tail(sr_engine* e, const Step& st, hipStream_t q) {
         SR_TRY(launch_beam_select(q, *st.beam));
         SR_TRY(launch_kv_suffix(q, *st.suffix));
     }
+    if (step_records(e, st)) {      // the pending tokens' records, at the log index k_step will give them (live rows only)
+        LogprobArgs la{e->d_logits, c.t_vocab, c.t_vocab, st.B, e->lp_n, nullptr, e->lp_part, st.chosen, e->d_step, e->d_finished, c.max_new_tokens,
+                       e->lp_log, nullptr, e->lp_ids, e->lp_tlp};
+        SR_TRY(launch_logprobs(q, la));
+    }
     return 0;
 }
 
@@ -859,7 +875,7 @@ int enqueue_decode_step(sr_engine* e, const Step& st, hipStream_t q, float* logi
 // The step as a ready graph: slot [kind][px_mode] of the cache, reused while its key matches, otherwise captured again on cap_stream
 int step_graph(sr_engine* e, StepKind kind, const Step& st, hipGraphExec_t* exec) {
     StepGraph& sg = e->graphs[kind][e->px_mode];
-    const StepKey key = step_key(st);
+    const StepKey key = step_key(e, st);
     if (sg.exec == nullptr || memcmp(&sg.key, &key, sizeof key) != 0) {
         if (sg.exec) { (void)hipGraphExecDestroy(sg.exec); sg.exec = nullptr; }
         hipGraph_t g = nullptr;
@@ -923,6 +939,14 @@ int decode_static(sr_engine* e, const Step& st, hipGraphExec_t exec, int max_new
     SR_TRY((int)hipStreamSynchronize(s));
     if (steps_done) *steps_done = done;
     return 0;
+}
+
+// sr_decode under sr_logprobs: rows 0..B-1 of the log cleared (what the pads after a finished row read as), then the first tokens' records
+// from the prefill logits
+int begin_static_log(sr_engine* e, const Step& st, hipStream_t s) {
+    if (!step_records(e, st)) return 0;
+    SR_TRY(launch_logprob_clear(s, st.B * e->c.max_new_tokens, e->lp_log, e->lp_ids, e->lp_tlp));
+    return enqueue_step_tail(e, st, s);
 }
 
 }  // namespace
@@ -1026,6 +1050,7 @@ int sr_engine_destroy(sr_engine* e) {
     for (auto& kind : e->graphs) for (auto& g : kind) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (e->beam_mem) (void)hipFree(e->beam_mem);
     if (e->rp_mem) (void)hipFree(e->rp_mem);
+    if (e->lp_mem) (void)hipFree(e->lp_mem);
     if (e->h_rp) (void)hipHostFree(e->h_rp);
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     if (e->ev_copy) (void)hipEventDestroy(e->ev_copy);
@@ -1296,6 +1321,14 @@ static int commit_admission(sr_engine* e, const int32_t* rows, int n, hipStream_
         if (!(e->rows_temp > 0.f)) aa.sampled = e->d_sampled;
     }
     SR_TRY(launch_admit_rows(s, aa));
+    // the rows' logs: the staged position-0 records (when the admission recorded), the rest cleared.  Also with the switch off, once a log
+    // exists: the switch may go on again in the middle of this occupant's run, and its earlier positions must not show the previous one's records
+    if (e->lp_mem) {
+        const bool rec = e->staged_lp;
+        LogprobAdmitArgs la{e->d_adm + off, n, c.max_new_tokens, rec ? e->lps_lp + off : nullptr, e->lps_ids + (size_t)off * LP_MAXN,
+                            e->lps_tlp + (size_t)off * LP_MAXN, e->lp_log, e->lp_ids, e->lp_tlp};
+        SR_TRY(launch_logprob_admit(s, la));
+    }
     if (e->rows_temp > 0.f && !e->staged_rp) SR_TRY(launch_scatter_rows(s, e->d_adm + off, e->d_adm_pick + off, e->d_sampled, n));   // the drawn first tokens
     e->staged_n -= n;
     e->staged_off = e->staged_n ? off + n : 0;
@@ -1528,6 +1561,13 @@ static int prefill_impl(sr_engine* e, const PrefillArgs& pa) {
         sa.seed = e->rows_seed ^ (0x9E3779B9u * ++e->adm_count);
         SR_TRY(launch_sample(s, sa));
     }
+    e->staged_lp = e->lp_n >= 0;
+    if (e->staged_lp) {            // position-0 records of the staged sequences (a fork reads its prompt's row), carried until the commit
+        const bool drawn = rp_stage || e->rows_temp > 0.f;
+        LogprobArgs la{e->d_logits_adm, c.t_vocab, c.t_vocab, n_seq, e->lp_n, row_map, e->lp_part_adm, drawn ? e->d_adm_pick : nullptr, nullptr, nullptr, 0,
+                       e->lps_lp, nullptr, e->lps_ids, e->lps_tlp};
+        SR_TRY(launch_logprobs(s, la));
+    }
     if (n_groups) {                // the prompts' KV prefixes into the slots of their other forks (d_adm_slots holds every fork's slot in staged order)
         KvFanoutArgs fa{e->kcache, e->vtcache, (long long)e->kv_layer_elems, c.t_layers, c.t_kv_heads, c.max_ctx, e->d_adm_slots, 0, 0, 0,
                         e->d_fan + MAXB, n_groups, max_L};
@@ -1576,7 +1616,9 @@ int sr_rows_begin(sr_engine* e, void* stream) {
     SR_TRY((int)hipMemcpyAsync(e->d_slots, st.data() + 4 * MAXB, MAXB * 4, hipMemcpyHostToDevice, s));
     SR_TRY((int)hipMemsetAsync(e->d_row_limit, 0, MAXB * 4, s));
     SR_TRY((int)hipMemsetAsync(e->d_ngen, 0, MAXB * 4, s));
+    if (e->lp_mem) SR_TRY(launch_logprob_clear(s, e->c.max_batch * e->c.max_new_tokens, e->lp_log, e->lp_ids, e->lp_tlp));
     SR_TRY((int)hipStreamSynchronize(s));
+    e->staged_lp = false;
     e->rows_mode = true;
     e->staged_n = e->staged_off = 0;
     e->prefilled_B = e->c.max_batch;
@@ -1757,6 +1799,7 @@ int sr_decode(sr_engine* e, const int32_t* host_slots, int B, int max_new, const
     }
     Step st = make_step(B, n_eos, pad_id, nullptr);      // bookkeeping kernel + forward: k_step reduces the LM head's arg-max partials itself
     st.forced = forced_dev;
+    if (int rc = begin_static_log(e, st, s)) return rc;
     hipGraphExec_t exec = nullptr;
     if (use_graph && !logits_trace && !forced) if (int rc = step_graph(e, STEP_GREEDY, st, &exec)) return rc;
     return decode_static(e, st, exec, max_new, logits_trace ? logits_trace + B * V : nullptr, tokens_out, s, steps_done);
@@ -1787,7 +1830,8 @@ int sr_decode_sample(sr_engine* e, int B, int max_new, const int32_t* host_eos, 
     st.sample.inv_temp = 1.0f / temperature; st.sample.top_k = top_k; st.sample.top_p = top_p; st.sample.rep_penalty = rep_penalty;
     st.sample.seen = rp ? e->d_seen : nullptr; st.sample.seed = seed;
     if (rp) SR_TRY(launch_mark_prompt(s, e->t_src, e->t_lastrow, e->d_seen, e->seen_words, B));
-    if (int rc = enqueue_step_tail(e, st, s)) return rc;      // first token, from the prefill logits
+    if (e->lp_n >= 0) SR_TRY(launch_logprob_clear(s, B * c.max_new_tokens, e->lp_log, e->lp_ids, e->lp_tlp));
+    if (int rc = enqueue_step_tail(e, st, s)) return rc;      // first token, from the prefill logits (and its record)
     hipGraphExec_t exec = nullptr;
     if (use_graph) if (int rc = step_graph(e, STEP_SAMPLED, st, &exec)) return rc;
     return decode_static(e, st, exec, max_new, nullptr, tokens_out, s, steps_done);
@@ -1971,6 +2015,73 @@ int sr_rows_read(sr_engine* e, int row, int32_t* dev_tokens_out, int n, void* st
     if (!e || !e->rows_mode || row < 0 || row >= e->c.max_batch || n < 0 || n > e->c.max_new_tokens)
         return fail(e, -22, "sr_rows_read: bad argument / not in rows mode");
     SR_TRY((int)hipMemcpyAsync(dev_tokens_out, e->d_tokens + (size_t)row * e->c.max_new_tokens, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+// chunk partials of sr_op_token_logprobs (engines own theirs), grown to the largest call
+static BeamPart* g_op_lp_part = nullptr;
+static size_t g_op_lp_cap = 0;
+
+int sr_logprobs(sr_engine* e, int top_n, void* stream) {
+    enter(e);
+    if (!e) return fail(e, -22, "sr_logprobs: null engine");
+    if (top_n < -1 || top_n > LP_MAXN) return fail(e, -22, "sr_logprobs: top_n %d outside -1 (off) .. %d", top_n, LP_MAXN);
+    hipStream_t s = (hipStream_t)stream;
+    if (top_n >= 0 && !e->lp_mem) {
+        const sr_config& c = e->c;
+        const size_t n_rec = (size_t)c.max_batch * c.max_new_tokens, n_part = (size_t)MAXB * beam_nb(c.t_vocab) * LP_PW;
+        size_t off = 0;
+        auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+        const size_t o_lp = take(n_rec * 4), o_ids = take(n_rec * LP_MAXN * 4), o_tlp = take(n_rec * LP_MAXN * 4), o_slp = take(MAXB * 4),
+                     o_sids = take(MAXB * LP_MAXN * 4), o_stlp = take(MAXB * LP_MAXN * 4), o_part = take(n_part * sizeof(BeamPart)),
+                     o_parta = take(n_part * sizeof(BeamPart));
+        void* mem = nullptr;
+        SR_TRY((int)hipMalloc(&mem, off));
+        char* m = static_cast<char*>(mem);
+        e->lp_log = reinterpret_cast<float*>(m + o_lp); e->lp_ids = reinterpret_cast<int*>(m + o_ids); e->lp_tlp = reinterpret_cast<float*>(m + o_tlp);
+        e->lps_lp = reinterpret_cast<float*>(m + o_slp); e->lps_ids = reinterpret_cast<int*>(m + o_sids); e->lps_tlp = reinterpret_cast<float*>(m + o_stlp);
+        e->lp_part = reinterpret_cast<BeamPart*>(m + o_part); e->lp_part_adm = reinterpret_cast<BeamPart*>(m + o_parta);
+        int rc = launch_logprob_clear(s, (int)n_rec, e->lp_log, e->lp_ids, e->lp_tlp);
+        if (!rc) rc = (int)hipStreamSynchronize(s);
+        if (rc) { (void)hipFree(mem); return fail(e, rc, "sr_logprobs: clearing the log failed with %d", rc); }
+        e->lp_mem = mem;
+    }
+    e->lp_n = top_n;
+    return 0;
+}
+
+int sr_rows_read_logprobs(sr_engine* e, int row, float* dev_lp, int32_t* dev_top_ids, float* dev_top_lp, int n, void* stream) {
+    enter(e);
+    if (!e || !dev_lp) return fail(e, -22, "sr_rows_read_logprobs: null argument");
+    if (!e->lp_mem) return fail(e, -22, "sr_rows_read_logprobs: nothing was recorded (call sr_logprobs first)");
+    if (row < 0 || row >= e->c.max_batch || n < 0 || n > e->c.max_new_tokens)
+        return fail(e, -22, "sr_rows_read_logprobs: row %d / n %d outside 0..%d / 0..%d", row, n, e->c.max_batch - 1, e->c.max_new_tokens);
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t at = (size_t)row * e->c.max_new_tokens;
+    SR_TRY((int)hipMemcpyAsync(dev_lp, e->lp_log + at, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    if (dev_top_ids) SR_TRY((int)hipMemcpyAsync(dev_top_ids, e->lp_ids + at * LP_MAXN, (size_t)n * LP_MAXN * 4, hipMemcpyDeviceToDevice, s));
+    if (dev_top_lp) SR_TRY((int)hipMemcpyAsync(dev_top_lp, e->lp_tlp + at * LP_MAXN, (size_t)n * LP_MAXN * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+int sr_op_token_logprobs(const float* logits, int64_t ld, int rows, int V, const int64_t* dev_tokens, const int32_t* row_map, int top_n, float* lp,
+                         int32_t* tok_out, int32_t* top_ids, float* top_lp, void* stream) {
+    if (!logits || !lp || rows < 1 || rows > MAXB || V < 16 || ld < V || (top_ids == nullptr) != (top_lp == nullptr))
+        return fail(nullptr, -22, "sr_op_token_logprobs: rows %d outside 1..%d, V %d < 16, ld %lld < V or a null argument", rows, MAXB, V, (long long)ld);
+    if (top_n < 0 || top_n > LP_MAXN) return fail(nullptr, -22, "sr_op_token_logprobs: top_n %d outside 0..%d", top_n, LP_MAXN);
+    const size_t need = (size_t)rows * beam_nb(V) * LP_PW;
+    if (need > g_op_lp_cap) {
+        (void)hipDeviceSynchronize();
+        if (g_op_lp_part) (void)hipFree(g_op_lp_part);
+        g_op_lp_part = nullptr; g_op_lp_cap = 0;
+        if (hipMalloc(&g_op_lp_part, need * sizeof(BeamPart)) != hipSuccess) return fail(nullptr, -12, "sr_op_token_logprobs: out of device memory");
+        g_op_lp_cap = need;
+    }
+    LogprobArgs la{logits, (long long)ld, V, rows, top_n, row_map, g_op_lp_part, reinterpret_cast<const long long*>(dev_tokens), nullptr, nullptr, 0,
+                   lp, tok_out, top_ids, top_lp};
+    const int rc = launch_logprobs((hipStream_t)stream, la);
+    if (rc) return fail(nullptr, rc, "sr_op_token_logprobs failed with %d", rc);
     return 0;
 }
 

@@ -276,6 +276,32 @@ struct KvSuffixArgs {
 };
 int launch_kv_suffix(hipStream_t s, const KvSuffixArgs& a);
 int launch_rows_abort(hipStream_t s, const unsigned row_mask[4], int* finished);      // finished[b] = 1 for every bit b of the 128-bit row mask
+// ------------------------------------------------------------------ logprob.hip
+// log-probs of the tokens the engine picks (sr_logprobs): record i = the float32 logits row row_map[i] (null: i) and its token -> lp = x[tok] -
+// logsumexp(x) and the row's top_n logits by (logit desc, token asc) as (id, x[id] - logsumexp(x)).  Two launches: chunk partials (the beam
+// search's chunk pass, K = max(top_n, 1)) then one wave per record that merges them in chunk order.  A record depends on its logits row only
+constexpr int LP_MAXN = 8;                    // top_n <= 8; the top arrays always have LP_MAXN entries per record (ids -1, log-probs 0 past top_n)
+constexpr int LP_PW = 1 + LP_MAXN;            // partial entries per (record, chunk): [n][NB][LP_PW], laid out as BeamArgs::part with K = LP_MAXN
+struct LogprobArgs {
+    const float* logits; long long ld; int V, n, top_n;
+    const int* row_map;
+    BeamPart* part;
+    const long long* chosen;                  // [n] the records' tokens, or null: the arg-max (lowest id among the maxima, as k_step finishes it)
+    // the engine's log (step != null): record i goes to position step[i] of row i of [n][max_new] logs, and only while !finished[i] and
+    // step[i] < max_new (the pending token of a live row: k_step logs it at that index); step null: record i goes to index i
+    const int* step; const int* finished; int max_new;
+    float* lp; int* tok_out; int* top_ids; float* top_lp;      // lp [..], tok_out [..] (optional), top_ids / top_lp [..][LP_MAXN] (optional, both or neither)
+};
+int launch_logprobs(hipStream_t s, const LogprobArgs& a);
+// sr_admit_commit: row rows[i] of the log takes record src + i (the staged sequence's position 0; src_lp null: cleared too) and the rest of
+// the row is cleared to (0, -1, 0)
+struct LogprobAdmitArgs {
+    const int* rows; int n, max_new;
+    const float* src_lp; const int* src_ids; const float* src_tlp;
+    float* lp; int* top_ids; float* top_lp;
+};
+int launch_logprob_admit(hipStream_t s, const LogprobAdmitArgs& a);
+int launch_logprob_clear(hipStream_t s, int n_rec, float* lp, int* top_ids, float* top_lp);     // n_rec records -> (0, -1, 0)
 // ------------------------------------------------------------------ sample.hip
 struct SampleArgs {
     const float* logits; int V; int B;      // float32 [B, V]

@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 from types import SimpleNamespace
-from typing import Iterable, Sequence
+from typing import Iterable, Optional, Sequence
 
 import numpy as np
 import torch
@@ -218,6 +218,7 @@ class Engine:
                                           C.c_float(temperature), int(top_k), C.c_float(top_p), C.c_float(repetition_penalty), int(seed) & 0xffffffff,
                                           C.c_void_p(toks.data_ptr()), 1 if use_graph else 0, self._s(), C.byref(done)), self._h, "sr_decode_sample")
         self.steps_done = done.value
+        self._keep_logprobs(B, max_new)
         return toks
 
     def decode_beam(self, num_beams: int, max_new: int, num_return_sequences: int = 1, length_penalty: float = 1.0, eos: Sequence[int] = (),
@@ -270,7 +271,46 @@ class Engine:
                                    C.c_void_p(forced.data_ptr()) if forced is not None else None, 1 if use_graph else 0,
                                    self._s(), C.byref(done)), self._h, "sr_decode")
         self.steps_done = done.value
+        self._keep_logprobs(B, max_new)
         return (toks, tr) if trace else toks
+
+    # ------------------------------------------------------------------ token log-probs (sr_logprobs)
+    top_logprobs: Optional[int] = None      # the N in force (None = off)
+    token_logprobs = None                   # left by a recording decode / decode_sample: (lp [B, max_new], top_ids / top_lp [B, max_new, 8])
+
+    def logprobs(self, top_n: Optional[int]):
+        """Record the log-prob of every token the engine generates from now on (x[tok] - logsumexp(x) of the float32 logits row, no
+        temperature / penalty / truncation) and the top_n most likely tokens of its row (0..8); None switches the recording off.  May be
+        called between any two steps or calls.  decode / decode_sample then leave self.token_logprobs; the continuous batcher reads rows
+        with row_logprobs."""
+        L.check(self.lib.sr_logprobs(self._h, -1 if top_n is None else int(top_n), self._s()), self._h, "sr_logprobs")
+        self.top_logprobs = None if top_n is None else int(top_n)
+
+    def row_logprobs(self, row: int, n: int):
+        """The first n records of a row (after decode / decode_sample: of a batch index) -> (lp float32 [n], top_ids int32 [n, 8],
+        top_lp float32 [n, 8]) on the device; ids past the N in force are -1.  Stream-ordered copies, as row_tokens."""
+        lp = torch.empty(n, dtype=torch.float32, device=self.device)
+        ids = torch.empty(n, 8, dtype=torch.int32, device=self.device)
+        tlp = torch.empty(n, 8, dtype=torch.float32, device=self.device)
+        self._read_logprobs(row, n, lp, ids, tlp)
+        return lp, ids, tlp
+
+    def _read_logprobs(self, row, n, lp, ids, tlp):
+        if n == 0:
+            return
+        L.check(self.lib_held.sr_rows_read_logprobs(self._h, int(row), C.c_void_p(lp.data_ptr()), C.c_void_p(ids.data_ptr()),
+                                                    C.c_void_p(tlp.data_ptr()), int(n), self._s()), self._h, "sr_rows_read_logprobs")
+
+    def _keep_logprobs(self, B, max_new):
+        self.token_logprobs = None
+        if self.top_logprobs is None:
+            return
+        lp = torch.empty(B, max_new, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, max_new, 8, dtype=torch.int32, device=self.device)
+        tlp = torch.empty(B, max_new, 8, dtype=torch.float32, device=self.device)
+        for b in range(B):
+            self._read_logprobs(b, max_new, lp[b], ids[b], tlp[b])
+        self.token_logprobs = (lp, ids, tlp)
 
     # ------------------------------------------------------------------ continuous batching (rows with independent lifecycles)
     def rows_begin(self):

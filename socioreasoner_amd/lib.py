@@ -118,6 +118,9 @@ SIGNATURES = {
     "sr_admit_sampling": (C.c_int, [_vp, _i64p, _i64p, _i32p, _i32p, _i32p, _i32p, _vp, _i, _vp, _i, _vp, _vp]),
     "sr_admit_stage_sampling": (C.c_int, [_vp, _i64p, _i64p, _i32p, _i32p, _i32p, _i32p, _vp, _i, _vp, _i, _vp, _vp]),
     "sr_rows_per_row": (C.c_int, [_vp, _i, _vp]),
+    "sr_logprobs": (C.c_int, [_vp, _i, _vp]),
+    "sr_rows_read_logprobs": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "sr_op_token_logprobs": (C.c_int, [_vp, C.c_int64, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -138,7 +141,7 @@ def load():
 
 _lib_held = None
 # the scheduler's per-round calls that only QUEUE work (no wait inside): see load_held
-HELD = ("sr_rows_step", "sr_rows_set_cus", "sr_rows_read", "sr_admit_commit")
+HELD = ("sr_rows_step", "sr_rows_set_cus", "sr_rows_read", "sr_admit_commit", "sr_rows_read_logprobs")
 
 
 def load_held():

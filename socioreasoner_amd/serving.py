@@ -64,9 +64,16 @@ class Request:
     # batcher's configuration.  temperature <= 1e-5 or top_k == 1: greedy (the arg-max of the penalised logits).  With a seed its forks draw
     # from the streams (seed, fork): tokens that depend on no row, slot or neighbour; without one the batcher picks a seed of its own per request
     sampling: Optional[dict] = None
+    # token log-probs (vLLM's SamplingParams.logprobs): None = none, N in 0..8 = the log-prob of every generated token under the raw logits and
+    # the N most likely tokens of its step.  Delivered in out_logprobs, set before on_complete is called: n = 1: {"logprobs": [lp per token],
+    # "top": [[(id, lp) x N] per token]}; n > 1: a list of those, one per fork in fork order
+    logprobs: Optional[int] = None
+    out_logprobs: object = None
 
 
 class ContinuousBatcher:
+    _lp: Optional[int] = None      # the N the engine records token log-probs under (None: off); raised by submit, switched off by _hand_back
+
     def __init__(self, engine, eos: Sequence[int], pad_id: int, steps_per_poll: int = 8, sampling: Optional[dict] = None,
                  time_phases: bool = False, overlap: bool = False, admit_cus_per_se="auto", per_row: Optional[bool] = None):
         """sampling: None = greedy, else {"temperature", "top_k" (1..1024), "top_p", "seed"} shared by all requests that bring no
@@ -219,6 +226,12 @@ class ContinuousBatcher:
                 raise ValueError(f"request sampling: top_p {p} outside (0, 1]")
             if not _penalty(s) > 0:
                 raise ValueError(f"request sampling: repetition_penalty {s.get('repetition_penalty')} <= 0")
+        if req.logprobs is not None:
+            if isinstance(req.logprobs, bool) or not isinstance(req.logprobs, (int, np.integer)) or not 0 <= int(req.logprobs) <= 8:
+                raise ValueError(f"request logprobs = {req.logprobs!r} is not an integer in 0..8")
+            if self._lp is None or int(req.logprobs) > self._lp:      # on, or up to the larger N: the rows' next records carry it
+                self._lp = int(req.logprobs)
+                self.engine.logprobs(self._lp)
         self.pending.append(req)
 
     def idle(self) -> bool:
@@ -284,19 +297,34 @@ class ContinuousBatcher:
         """(request, fork index) of every sequence of a group, prompt-major: the engine's staging order"""
         return [(r, j) for r in grp for j in range(r.n)]
 
-    def _report(self, req, fork, toks, on_complete):
+    def _report(self, req, fork, toks, on_complete, lps=None):
         """an n = 1 request is reported as it always was; an n > 1 request once its last fork is done, with the n lists in fork order (an
-        aborted one not at all)"""
+        aborted one not at all).  lps: the fork's records (host arrays lp, top ids, top lp) of a request that asked for log-probs"""
+        rec = None
+        if lps is not None and not req.aborted:
+            k = int(req.logprobs)
+            rec = {"logprobs": [float(x) for x in lps[0]],
+                   "top": [[(int(i), float(v)) for i, v in zip(ids[:k], tl[:k])] for ids, tl in zip(lps[1], lps[2])]}
         if req.n == 1:
+            if rec is not None:
+                req.out_logprobs = rec
             on_complete(req, toks)
             return
-        part = self._parts.setdefault(id(req), [req, [None] * req.n, req.n])
+        part = self._parts.setdefault(id(req), [req, [None] * req.n, req.n, [None] * req.n])
         part[1][fork] = toks
+        part[3][fork] = rec
         part[2] -= 1
         if part[2] == 0:
             del self._parts[id(req)]
             if not req.aborted:
+                if req.logprobs is not None:
+                    req.out_logprobs = part[3]
                 on_complete(req, part[1])
+
+    def _read_logprobs(self, rows, counts):
+        """the records of the finished rows whose requests asked for them (None for the others): device copies in stream order, as rows_tokens"""
+        return [self.engine.row_logprobs(row, n) if self.active[row].logprobs is not None and not self.active[row].aborted else None
+                for row, n in zip(rows, counts)]
 
     # ------------------------------------------------------------------ overlapped admission (stage on a side stream, commit into rows)
     def _take_group(self, limit: int):
@@ -576,9 +604,10 @@ class ContinuousBatcher:
             if rows:
                 counts = [int(cnt[r]) for r in rows]
                 buf = self.engine.rows_tokens(rows, counts)
+                lps = self._read_logprobs(rows, counts)
                 ev = torch.cuda.Event()
                 ev.record(s)
-                self._deferred.append(([(self.active.pop(r), self.row_fork.pop(r, 0)) for r in rows], counts, buf, ev))
+                self._deferred.append(([(self.active.pop(r), self.row_fork.pop(r, 0)) for r in rows], counts, buf, ev, lps))
                 for row in rows:
                     self.row_own.pop(row, None)
                     self.free.append(row)
@@ -594,17 +623,21 @@ class ContinuousBatcher:
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(self.engine.device)
         todo, self._deferred = self._deferred, []
-        for reqs, counts, buf, ev in todo:
+        for reqs, counts, buf, ev, lps in todo:
             with torch.cuda.stream(self._copy_stream):
                 self._copy_stream.wait_event(ev)
                 buf.record_stream(self._copy_stream)
                 host = buf.cpu().numpy()
+                for rec in lps:
+                    for t in rec or ():
+                        t.record_stream(self._copy_stream)
+                lps = [None if rec is None else tuple(t.cpu().numpy() for t in rec) for rec in lps]
             # the callbacks run with the rows' stream current, as they did when they were called from the poll: device work they queue (the bench's
             # raster tail and result exchange) is ordered behind the decode steps and never lands on the null stream, which would synchronise with the
             # CU-masked (blocking) streams -- i.e. wait for a staged admission and hold every later decode chunk behind itself
             with (torch.cuda.stream(self._dec_last) if (self.overlap and self._dec_last is not None) else contextlib.nullcontext()):
-                for (req, fork), n, toks in zip(reqs, counts, host):
-                    self._report(req, fork, toks[:n].tolist(), on_complete)
+                for (req, fork), n, toks, rec in zip(reqs, counts, host, lps):
+                    self._report(req, fork, toks[:n].tolist(), on_complete, rec)
 
     def _poll(self):
         import time
@@ -643,14 +676,20 @@ class ContinuousBatcher:
             req = self.active.pop(row)
             self.row_own.pop(row, None)
             toks = self.engine.row_tokens(row, int(cnt[row])).cpu().tolist()
+            rec = None
+            if req.logprobs is not None and not req.aborted:
+                rec = tuple(t.cpu().numpy() for t in self.engine.row_logprobs(row, int(cnt[row])))
             self.free.append(row)
-            self._report(req, self.row_fork.pop(row, 0), toks, on_complete)
+            self._report(req, self.row_fork.pop(row, 0), toks, on_complete, rec)
 
     def _hand_back(self):
-        """back to the caller's stream, the engine's CU hint back to the whole chip"""
+        """back to the caller's stream, the engine's CU hint back to the whole chip, its log-prob recording off again"""
         if self.overlap and self._dec_last is not None:
             torch.cuda.current_stream(self.engine.device).wait_stream(self._dec_last)
             self._set_cus(0)
+        if self._lp is not None:
+            self.engine.logprobs(None)
+            self._lp = None
 
     def run_stream(self, requests: Sequence[Request], on_complete: Callable[[Request, List[int]], None]) -> None:
         """Serve a stream of requests, reporting each as it completes (in completion order): what a server does -- the next requests'
